@@ -2,6 +2,7 @@
 """Benchmark of the classify hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload lca|...]
+                    [--dump-outputs DIR] [--full]
 
 The headline workload is BASELINE.json configs[2], the largest configuration
 that fits one GPU: synthetic SAM of 50 M reads x <=16 hits (~250 M alignment
@@ -10,8 +11,10 @@ records), a 2 M-node NCBI-shaped taxonomy, `--rank phylum,genus,species`.  A
 in HBM (1.2 GB of packed arrays staged before the timed region, far beyond the
 256 MiB Infinity Cache); `passes` is sized so that the K timed steps last about
 a second.  The metric is alignment records classified per second, whole job.
+A plain run sets up, warms up, times the K steps and prints the line;
+`--dump-outputs DIR` writes what the timed path computed (dump_outputs).
 
-Next to the headline the same JSON line carries
+With `--full` the same JSON line also carries
   roofline      dominant kernel of the headline workload: algorithmic bytes /
                 HIP-event duration on the library's stream vs 8 TB/s
   configs       the same figures for the other single-GPU configurations
@@ -1147,12 +1150,97 @@ def e2e_twopass(device, n_samples=8, n_reads=20_000_000, workdir=None, reps=1,
     return res
 
 
-def lca_problem(seed=1002, scale=1.0):
-    """The packed configs[2] problem of `seed` (what LcaWorkload stages)."""
+def host_threads():
+    """Threads for the host's share of the set-up: OMP_NUM_THREADS when it is
+    set, else the CPUs this process may run on; at most 16."""
+    n = int(os.environ.get('OMP_NUM_THREADS') or 0) or \
+        len(os.sched_getaffinity(0))
+    return max(1, min(n, 16))
+
+
+def lca_problem(seed=1002, scale=1.0, threads=None):
+    """The packed configs[2] problem of `seed` (what LcaWorkload stages):
+    the arrays of ``synth.as_sets(synth.lca_problem(default_rng(seed),
+    n_nodes=2_000_000, n_subjects=100_000, n_reads=50M * scale,
+    with_names=False))``, with the same draws in the same order, but the
+    per-read work split into ranges of reads over host threads (numpy lets go
+    of the GIL there) -- on one thread it is half a minute of the benchmark's
+    set-up.  tests/test_bench_host.py holds the two equal."""
+    from concurrent.futures import ThreadPoolExecutor
     n_reads = int(50_000_000 * scale)
-    return synth.as_sets(synth.lca_problem(
-        np.random.default_rng(seed), n_nodes=2_000_000, n_subjects=100_000,
-        n_reads=n_reads, with_names=False))
+    rng = np.random.default_rng(seed)
+    parent, rank = synth.taxonomy_arrays(rng, 2_000_000)
+    parent, rank, subj_in = synth._with_subjects(rng, parent, rank, 100_000)
+    h = synth.hierarchy_from_arrays(parent, rank, synth.RANK_CODES,
+                                    with_names=False)
+    subjects = np.sort(h.pre_of_input[subj_in])
+    hp = h.parent.astype(np.int64)
+    hl = h.last.astype(np.int64)
+    k = np.where(rng.random(n_reads) < 0.5, 1,
+                 rng.integers(2, 17, n_reads)).astype(np.int64)
+    anchor = subjects[synth.zipf_draw(rng, subjects.size, n_reads)]
+    up = rng.geometric(0.35, n_reads)
+    u_start = rng.random(n_reads)
+    # searchsorted(subjects, node) for every node, looked up per read below
+    nodes = np.arange(hp.size, dtype=np.int64)
+    first_at = np.searchsorted(subjects, nodes, side='left')
+    last_at = np.searchsorted(subjects, nodes, side='right')
+    threads = threads or host_threads()
+    cuts = np.linspace(0, n_reads, 4 * threads + 1).astype(np.int64)
+    ranges = list(zip(cuts[:-1].tolist(), cuts[1:].tolist()))
+
+    def climb(r):
+        # synth.lca_problem's ancestor climb, over the reads still climbing
+        r0, r1 = r
+        anc, upr, kr = anchor[r0:r1].copy(), up[r0:r1], k[r0:r1]
+        live, step = np.flatnonzero(upr >= 1), 1
+        while live.size:
+            anc[live] = hp[anc[live]]
+            step += 1
+            live = live[upr[live] >= step]
+        lo, hi = first_at[anc], last_at[hl[anc]]
+        short = np.flatnonzero((hi - lo < kr) & (anc != 0))
+        while short.size:
+            anc[short] = hp[anc[short]]
+            lo[short] = first_at[anc[short]]
+            hi[short] = last_at[hl[anc[short]]]
+            short = short[(hi[short] - lo[short] < kr[short]) &
+                          (anc[short] != 0)]
+        k[r0:r1] = np.minimum(kr, np.maximum(hi - lo, 1))
+        return lo, hi
+
+    def records(r, lohi):
+        # the k distinct subjects of every read, then as_sets: ascending
+        r0, r1 = r
+        lo, hi = lohi
+        kr = k[r0:r1]
+        local = np.repeat(np.arange(r1 - r0), kr)
+        j = np.arange(local.size, dtype=np.int64) - \
+            (qoff[r0:r1] - qoff[r0])[local]
+        span = np.maximum(hi - lo, 1)[local]
+        start = (u_start[r0:r1] * (hi - lo)).astype(np.int64)[local]
+        pick = lo[local] + (start + (j * span) // kr[local]) % span
+        subj = subjects[np.minimum(pick, subjects.size - 1)]
+        single = (kr == 1)[local]
+        subj[single] = anchor[r0:r1][local[single]]
+        pairs = np.unique(((local + r0) << 32) |
+                          subj.astype(np.int32).astype(np.int64))
+        return ((pairs & 0xFFFFFFFF).astype(np.int32),
+                np.bincount((pairs >> 32) - r0, minlength=r1 - r0))
+
+    with ThreadPoolExecutor(threads) as ex:
+        lohi = list(ex.map(climb, ranges))
+        qoff = np.zeros(n_reads + 1, dtype=np.int64)
+        np.cumsum(k, out=qoff[1:])
+        parts = list(ex.map(records, ranges, lohi))
+    del lohi
+    cnt = np.concatenate([c for _, c in parts])
+    subj = np.concatenate([s for s, _ in parts])
+    del parts
+    q = np.zeros(n_reads + 1, dtype=np.int64)
+    np.cumsum(cnt, out=q[1:])
+    return dict(hier=h, subj=subj, qoff=q.astype(np.int32), n_ids=h.n_nodes,
+                subjects=subjects)
 
 
 def e2e_inputs(kind, d, reads=0, prob=None):
@@ -1905,6 +1993,58 @@ def timed_steps(wl, steps, warmup, passes, sync):
     return sync.allmax(elapsed)
 
 
+DUMP_LIMIT = 64 << 20           # bytes of --dump-outputs files, all together
+
+
+def count_passes(wl):
+    """Count the passes `wl` runs from here on in `wl.passes_run`: its count
+    table adds up every pass since the workload cleared it."""
+    step = wl.step
+    wl.passes_run = 0
+
+    def counted():
+        wl.passes_run += 1
+        step()
+    wl.step = counted
+
+
+def dump_outputs(wl, out_dir):
+    """--dump-outputs: the count table of one pass over the sample -- what a
+    classify call of the timed path returns; every pass computes the same, the
+    last timed step's included -- as `<rank or job>.npy`, one file per job:
+    float64 rows (group, feature, count) sorted by group and feature, count =
+    the sum of the row's n / k (k = 0: n / WEIGHT_L).  The table holds the sum
+    of `wl.passes_run` passes and is divided by it, exactly (integers); tables
+    over DUMP_LIMIT keep a fixed, seeded sample of their rows."""
+    keys, vals = wl.ctx.counts_fetch()
+    n = wl.passes_run
+    if n < 1 or np.any(vals % n):
+        raise RuntimeError(f'the count table is not {n} equal passes')
+    keys, vals = nat.canonical_counts(keys, vals // n)
+    job, k, grp, feat = nat.decode_keys(keys)
+    count = vals.astype(np.float64) / np.where(k == 0, nat.WEIGHT_L, k)
+    o = np.lexsort((feat, grp, job))
+    job, grp, feat, count = job[o], grp[o], feat[o], count[o]
+    first = np.ones(o.size, dtype=bool)
+    first[1:] = (np.diff(job) != 0) | (np.diff(grp) != 0) | \
+        (np.diff(feat) != 0)
+    rows = np.flatnonzero(first)
+    total = np.add.reduceat(count, rows) if rows.size else count
+    table = np.stack([grp[rows], feat[rows], total], axis=1).astype(np.float64)
+    job = job[rows]
+    room = (DUMP_LIMIT - 4096) // (3 * 8)      # rows (4 KB: the headers)
+    if len(table) > room:
+        pick = np.sort(np.random.default_rng(0).choice(len(table), room,
+                                                       replace=False))
+        table, job = table[pick], job[pick]
+    ranks = getattr(wl, 'ranks', ())
+    labels = ranks if len(ranks) == len(wl.jobs) else \
+        [f'job{j}' for j in range(len(wl.jobs))]
+    os.makedirs(out_dir, exist_ok=True)
+    for j, label in enumerate(labels):
+        np.save(os.path.join(out_dir, f'{label}.npy'), table[job == j])
+
+
 def kernel_times(wl, n=6, burst=8):
     """HIP events around each launch on the library's stream (first context),
     averaged over a separate loop of launches.  The brackets that are read are
@@ -1931,15 +2071,16 @@ def kernel_times(wl, n=6, burst=8):
     return {f: float(np.mean(v)) for f, v in durs.items() if v}
 
 
-def config_block(wl, seconds, passes, steps, scale, key):
+def kernel_roofline(wl, ms_pass, scale, key):
+    """The dominant kernel of a pass against HBM: HIP-event brackets over
+    launches of its own (kernel_times), after the timed steps."""
     jobs = getattr(wl, 'jobs_per_pass', 1)
     if jobs > 1:
         # a family launched once per job: the event brackets hold its last
         # launch only.  The dominant kernel's figure is the pass per job (its
         # stream + the two small kernels behind it); the kernel's own average
         # is in profiles/*_kernel_stats.csv
-        ms_job = seconds * 1e3 / (steps * passes) / jobs
-        means = {wl.dominant: ms_job}
+        means = {wl.dominant: ms_pass / jobs}
     else:
         means = kernel_times(wl)
     dominant = max(means, key=means.get)
@@ -1949,33 +2090,49 @@ def config_block(wl, seconds, passes, steps, scale, key):
     else:
         alg = wl.launch_bytes
     achieved = alg / (kern_ms * 1e-3) / 1e9
-    ms_pass = seconds * 1e3 / (steps * passes)
     traffic, source = measured_traffic(key, scale)
+    overlapped = getattr(wl, 'n_chunks', 1)
+    roof = {'bound': 'hbm', 'achieved': round(achieved, 1),
+            'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+            'frac': round(achieved / HBM_PEAK_GBS, 4),
+            'traffic': traffic, 'traffic_source': source,
+            'kernel': dominant,
+            'kernel_symbol': getattr(wl, 'symbols', {}).get(
+                dominant, f'wk::{dominant}_kernel'),
+            'kernel_ms': round(kern_ms, 4),
+            'algorithmic_bytes': alg,
+            'kernels_ms': {f: round(v, 4) for f, v in means.items()},
+            # the brackets are a chain of events over one pass: their sum is
+            # the pass as the stream saw it
+            'kernels_ms_sum': round(sum(means.values()), 4),
+            'sum_over_ms_per_pass': round(
+                sum(means.values()) * overlapped / ms_pass, 3)}
+    if jobs > 1:
+        roof['note'] = (
+            f'{jobs} jobs per pass, one launch of the stream each: kernel_ms is '
+            'the pass divided by the jobs (the stream and the two kernels '
+            'behind it), algorithmic_bytes those of one job')
+    if overlapped > 1:
+        roof['note'] = (
+            f'{overlapped} chunks on {overlapped} streams overlap in the timed '
+            'passes; the kernel brackets are those of one chunk launched '
+            'alone, rocprofv3 averages those of overlapping kernels: use '
+            'roofline_step')
+    return roof
+
+
+def config_block(wl, seconds, passes, steps, scale, key, kernels=True):
+    """The figures of the timed passes; `kernels`: also the dominant kernel's
+    roofline, which launches kernels of its own."""
+    ms_pass = seconds * 1e3 / (steps * passes)
     # the whole step: every kernel of a pass against the configuration's
     # algorithmic bytes (SURVEY §8d) — for a pass of several kernels this, not
     # the dominant kernel's figure, is what the records/s follow
     step_gbs = wl.alg_bytes / (ms_pass * 1e-3) / 1e9
-    overlapped = getattr(wl, 'n_chunks', 1)
     block = {'workload': wl.name, 'records': wl.records, 'reads': wl.reads,
              'ms_per_pass': round(ms_pass, 4),
              'value': round(wl.records / (ms_pass * 1e-3), 1),
              'timed_region_s': round(seconds, 3),
-             'roofline': {'bound': 'hbm', 'achieved': round(achieved, 1),
-                          'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                          'frac': round(achieved / HBM_PEAK_GBS, 4),
-                          'traffic': traffic, 'traffic_source': source,
-                          'kernel': dominant,
-                          'kernel_symbol': getattr(wl, 'symbols', {}).get(
-                              dominant, f'wk::{dominant}_kernel'),
-                          'kernel_ms': round(kern_ms, 4),
-                          'algorithmic_bytes': alg,
-                          'kernels_ms': {f: round(v, 4)
-                                         for f, v in means.items()},
-                          # the brackets are a chain of events over one pass:
-                          # their sum is the pass as the stream saw it
-                          'kernels_ms_sum': round(sum(means.values()), 4),
-                          'sum_over_ms_per_pass': round(
-                              sum(means.values()) * overlapped / ms_pass, 3)},
              'roofline_step': {'bound': 'hbm',
                                'algorithmic_bytes': wl.alg_bytes,
                                'achieved': round(step_gbs, 1),
@@ -1993,17 +2150,8 @@ def config_block(wl, seconds, passes, steps, scale, key):
             'bound': 'hbm', 'algorithmic_bytes': wl.alg_bytes,
             'achieved': round(gbs, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
             'frac': round(gbs / HBM_PEAK_GBS, 4)}
-    if jobs > 1:
-        block['roofline']['note'] = (
-            f'{jobs} jobs per pass, one launch of the stream each: kernel_ms is '
-            'the pass divided by the jobs (the stream and the two kernels '
-            'behind it), algorithmic_bytes those of one job')
-    if overlapped > 1:
-        block['roofline']['note'] = (
-            f'{overlapped} chunks on {overlapped} streams overlap in the timed '
-            'passes; the kernel brackets are those of one chunk launched '
-            'alone, rocprofv3 averages those of overlapping kernels: use '
-            'roofline_step')
+    if kernels:
+        block['roofline'] = kernel_roofline(wl, ms_pass, scale, key)
     return block
 
 
@@ -2053,19 +2201,25 @@ def run_rank(a, rank, world, local, sync):
     else:
         wl = WORKLOADS[a.workload](ctx, seed=1002 + rank, scale=a.scale)
     wl.sync()
+    dump = a.dump_outputs and rank == 0
+    if dump:
+        count_passes(wl)
     passes = a.passes or passes_for(wl, a.steps)
     if world > 1:                   # every rank the same number of passes
         passes = int(sync.allmax(float(passes)))
     elapsed = timed_steps(wl, a.steps, a.warmup, passes, sync)
+    if dump:
+        dump_outputs(wl, a.dump_outputs)
     checksum = wl.check()
     if rank != 0:
-        if not (a.headline_only or a.no_e2e) and a.workload in ('lca',
-                                                                 'lca_text'):
+        if a.full and not (a.headline_only or a.no_e2e) and \
+                a.workload in ('lca', 'lca_text'):
             e2e_ranks(a, None, wl, dev, world, sync)
         wl.close()
         ctx.close()
         return None
-    block = config_block(wl, elapsed, passes, a.steps, a.scale, a.workload)
+    block = config_block(wl, elapsed, passes, a.steps, a.scale, a.workload,
+                         kernels=a.full)
     ms_per_step = elapsed * 1e3 / a.steps
     value = wl.records * passes * world / (elapsed / a.steps)
     line = {
@@ -2096,12 +2250,12 @@ def run_rank(a, rank, world, local, sync):
                       if 'sort_ms' in block else {}),
                    'sharding': f'samples x {world} ranks on {n_distinct} '
                                'GPU(s), no collective'},
-        'roofline': block['roofline'],
+        **({'roofline': block['roofline']} if 'roofline' in block else {}),
         'roofline_step': block['roofline_step'],
         'device': ctx.device_name,
         'checksum': checksum,
     }
-    if a.headline_only:
+    if a.headline_only or not a.full:
         wl.close()
         ctx.close()
         return line
@@ -2412,16 +2566,26 @@ def parse_args(argv=None):
                     help='let --gpus N exceed the visible devices (ranks are '
                          'stacked; the line then reports n_gpus = distinct '
                          'devices and oversubscribed = true)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, measure the rest: the dominant '
+                         'kernel\'s roofline, the other configurations, the '
+                         'end-to-end legs and the CPU baseline (a plain run '
+                         'times the headline\'s steps only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the count table of '
+                         'one pass (the same in every step) to DIR/<rank or '
+                         'job>.npy: float64 rows (group, feature, count)')
     ap.add_argument('--no-cpu', action='store_true',
-                    help='skip the CPU baseline leg')
+                    help='with --full: skip the CPU baseline leg')
     ap.add_argument('--no-e2e', action='store_true',
-                    help='skip the end-to-end legs')
+                    help='with --full: skip the end-to-end legs')
     ap.add_argument('--e2e-frac', type=float, default=1.0,
                     help='fraction of the configuration the end-to-end legs '
                          'read (default: all of it, memory permitting)')
     ap.add_argument('--headline-only', action='store_true',
-                    help='skip the per-config blocks, the end-to-end leg and '
-                         'the CPU baseline')
+                    help='with --full: skip the per-config blocks, the '
+                         'end-to-end leg and the CPU baseline (the roofline '
+                         'of the headline stays)')
     ap.add_argument('--tmp', default=None,
                     help='directory for the synthetic text files (default: '
                          '/dev/shm or the temporary directory, whichever has '

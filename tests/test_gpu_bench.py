@@ -8,13 +8,14 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARGS = ['--headline-only', '--no-cpu', '--scale', '0.02', '--steps', '3',
-        '--warmup', '1']
+ARGS = ['--full', '--headline-only', '--no-cpu', '--scale', '0.02', '--steps',
+        '3', '--warmup', '1']
 KEYS = {'metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step',
         'higher_is_better', 'scaling', 'vs_baseline', 'dtype', 'data',
         'config', 'roofline'}
@@ -62,6 +63,32 @@ def test_one_rank_line():
     assert d2['n_gpus'] == len(set(d2['rank_devices'])) == min(2, n_devices())
     assert d2['oversubscribed'] == (n_devices() < 2)
     assert d2['config']['records_per_gpu'] == d['config']['records_per_gpu']
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run times the headline alone (no kernel roofline, no side
+    blocks) and `--dump-outputs` writes the count table of one pass: the same
+    arrays whatever the number of steps, each rank's counts adding up to the
+    sample's reads (every read is counted once per rank, whole or split)."""
+    base = ['--scale', '0.02', '--warmup', '1']
+    d = run([sys.executable, 'bench.py', '--gpus', '1', '--steps', '3',
+             '--dump-outputs', str(tmp_path / 'a')] + base)
+    assert {'metric', 'value', 'unit', 'higher_is_better', 'dtype',
+            'ms_per_step'} <= set(d)
+    assert 'roofline' not in d and 'configs' not in d and 'e2e' not in d
+    assert d['steps'] == 3 and d['dtype'] == 'u8'
+    assert abs(d['ms_per_step'] * 3 / 1e3 - d['config']['timed_region_s']) \
+        < 2e-3
+    d2 = run([sys.executable, 'bench.py', '--gpus', '1', '--steps', '5',
+              '--dump-outputs', str(tmp_path / 'b')] + base)
+    assert d2['steps'] == 5
+    reads = d['config']['reads_per_gpu']
+    for rank in ('phylum', 'genus', 'species'):
+        a = np.load(tmp_path / 'a' / f'{rank}.npy')
+        b = np.load(tmp_path / 'b' / f'{rank}.npy')
+        assert a.dtype == np.float64 and a.ndim == 2 and a.shape[1] == 3
+        assert a.shape[0] > 0 and np.array_equal(a, b)
+        assert abs(a[:, 2].sum() - reads) < 1e-6 * reads
 
 
 def test_more_ranks_than_devices_are_refused():

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The results table of DESIGN.md §5 from a bench.py line:
+"""The results table of DESIGN.md §5 from a `bench.py --full` line:
 
     python tools/design_table.py profiles/r05_bench_final.json
 """

@@ -3,7 +3,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$R/gpurun_out/ldspmc; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for wl in lca ordinal; do
-  timeout 600 rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_INSTS_VALU SQ_INSTS_SALU --output-format csv -d $OUT/$wl -- python $R/bench.py --workload $wl --steps 5 --warmup 2 --no-cpu > $OUT/$wl.log 2>&1
+  timeout 600 rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_INSTS_VALU SQ_INSTS_SALU --output-format csv -d $OUT/$wl -- python $R/bench.py --workload $wl --steps 5 --warmup 2 --full --no-cpu > $OUT/$wl.log 2>&1
   echo "$wl rc=$?"
   f=$(find $OUT/$wl -name "*counter_collection.csv" | head -1)
   [ -n "$f" ] && cp "$f" $OUT/pmc_$wl.csv
