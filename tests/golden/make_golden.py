@@ -1791,6 +1791,77 @@ def gen_hierarchy_build(seed=83, n_cases=90):
     dump('hierarchy_build.json', cases)
 
 
+def gen_dtok_limits():
+    """The texts of tests/golden/dtok_limits.py (the one-kernel tokenizer's
+    limit shapes) through the reference: per case the recipe, the sha256 of
+    every file, the tables `workflow` wrote (or the type of the exception it
+    raised) and a digest of what `parse_sam_file` / `parse_sam_file_ft` yield
+    per file.  tests/test_gpu_dtok_limits.py compares the device route's
+    tables with these, tests/test_dtok_limits_host.py the host tokenizer's
+    reads."""
+    import contextlib
+    import hashlib
+    import io
+    import tempfile
+    import dtok_limits as D
+    from woltka import align as A
+    from woltka.file import readzip
+    from woltka.workflow import workflow, parse_exclude
+    tax = os.path.join(DATA, 'taxonomy')
+    out = {}
+    for name, (shape, variant, seed, size, geo) in D.CASES.items():
+        files, kw = D.make_case(shape, seed, size, variant)
+        kw = dict(kw, output_fmt=False)
+        case = {'shape': shape, 'variant': variant, 'seed': seed,
+                'size': size, 'geometries': list(geo), 'kwargs': kw,
+                'text_sha256': {rel: hashlib.sha256(t.encode()).hexdigest()
+                                for rel, t in files.items()}}
+        with tempfile.TemporaryDirectory() as tmp:
+            for rel, text in files.items():
+                os.makedirs(os.path.dirname(os.path.join(tmp, rel)),
+                            exist_ok=True)
+                with open(os.path.join(tmp, rel), 'wb') as f:
+                    f.write(text.encode())
+            excl = parse_exclude(kw.get('exclude'))
+            parse = {}
+            for rel in sorted(files):
+                with readzip(os.path.join(tmp, rel)) as fh:
+                    try:
+                        reads = list(A.parse_sam_file_ft(fh, excl) if excl
+                                     else A.parse_sam_file(fh))
+                        parse[rel] = D.parse_digest(reads)
+                    except Exception as e:      # noqa: BLE001
+                        parse[rel] = {'error': type(e).__name__}
+            case['parse'] = parse
+
+            def real(v):
+                if isinstance(v, list):
+                    return [real(x) for x in v]
+                if isinstance(v, str) and v.startswith('$TAX/'):
+                    return os.path.join(tax, v[5:])
+                if v == 'aln':
+                    return os.path.join(tmp, v)
+                return v
+            args = {k: real(v) for k, v in kw.items()}
+            args['output_fp'] = os.path.join(tmp, 'out')
+            try:
+                with contextlib.redirect_stdout(io.StringIO()):
+                    workflow(**args)
+                o = args['output_fp']
+                paths = ({fn: os.path.join(o, fn) for fn in sorted(
+                    os.listdir(o))} if os.path.isdir(o) else {'out': o})
+                tables = {}
+                for fn, fp in paths.items():
+                    with open(fp, 'rb') as f:
+                        tables[fn] = D.table_record(f.read())
+                case['tables'] = tables
+            except Exception as e:              # noqa: BLE001
+                case['error'] = type(e).__name__
+        out[name] = case
+        print(name, case.get('error') or sorted(case['tables']), flush=True)
+    dump('dtok_limits.json', out)
+
+
 def main():
     if not _refshim.install():
         print('reference tree not present: nothing to do')
@@ -1813,6 +1884,7 @@ def main():
     gen_cli_config5()
     gen_cli_medium()
     gen_dtok_blocks()
+    gen_dtok_limits()
     gen_hierarchy_build()
 
 

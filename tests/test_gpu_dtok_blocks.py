@@ -77,3 +77,10 @@ def test_blocks_cut_anywhere_give_the_reference_tables(tmp_path, monkeypatch,
         assert ROUTES['host_block'] == 0, dict(ROUTES)
     if block == 1 << 14:
         assert ROUTES[route] + ROUTES['host_block'] >= 4, dict(ROUTES)
+    # SAM whose job set takes packed records (no coordinates, no `free`) and
+    # no line for the host: the one-kernel tokenizer kept blocks behind each
+    # file's first
+    kw = case['kwargs']
+    if block == 1 << 14 and kw['input_fmt'] == 'sam' and not case['odd'] \
+            and not kw.get('coords_fp') and kw.get('ranks') != 'free':
+        assert ROUTES['dtok_fused'] > 0, dict(ROUTES)

@@ -2409,6 +2409,10 @@ int wk_words_flush(wk_ctx* c) {
     }
     kt = ktimer_begin(c, "weigh_merge");
     wm.n_subjects = (uint32_t)c->n_subjects;
+    // (a subject table that grew past the streams' slices since they were opened -- past kMaxStreams slices: the
+    // accumulation is flushed by `words_roll` and goes on unsliced -- holds no records of the subjects behind them; the
+    // merge stops at the last stream's slice, its rows are all there are)
+    if (wm.streams) wm.n_subjects = (uint32_t)std::min<int64_t>(c->n_subjects, (int64_t)wm.streams * kSliceBins);
     wm.rows = a.rows;
     wm.row_w = a.row_w;
     wm.n_jobs = n_jobs;
