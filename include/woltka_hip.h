@@ -138,8 +138,10 @@ int wk_sync(wk_ctx* ctx); /* wait for all work on the context's stream */
  * the blocks copied from now on will be scanned for plain SAM records of the
  * weighted histogram -- wk_dtok_copy* launches no newline count behind their
  * copies (the one-kernel tokenizer needs none; a block that takes the six
- * kernels after all is counted when it is scanned).  Results never depend on
- * it.  Unknown names are an error. */
+ * kernels after all is counted when it is scanned).  "cover_cap_rows" (0 or
+ * 4096 .. 2^28): the rows the coverage pile of wk_cover_begin(ctx, 0) holds
+ * (0: the default, 2^22) -- small values make small inputs compact and spill.
+ * Results never depend on either.  Unknown names are an error. */
 int wk_set_option(wk_ctx* ctx, const char* name, int64_t value);
 
 /* (Measurement entry points -- launch-shape knobs, event timers, resident-text
@@ -390,6 +392,49 @@ int wk_strata_labels(wk_ctx* ctx, int32_t* slot, int64_t* text_off,
 int wk_strata_groups(wk_ctx* ctx, const int32_t* slot, const int32_t* group,
                      int32_t n);
 int wk_strata_clear(wk_ctx* ctx);
+
+/* ---- subject coverage on the device (csrc/wk_cover.hpp) ---------------------
+ * range.parse_ranges / merge_ranges / calc_coverage (range.py:89-200) for ONE
+ * sample: the union of the aligned ranges (beg, end) of every subject -- sorted
+ * by (subject, beg, end), two ranges merged while `end >= next beg` -- kept in
+ * a pile of rows on the device.  The union does not depend on the order or the
+ * pieces the rows come in, nor on the pile's size.  Subject ids are the
+ * caller's (the route: the tokenizer's ids, i.e. the names in the file, before
+ * any subject map); rows with a negative subject are skipped.
+ *   wk_cover_begin   reserves a pile of `cap_rows` rows (0: the option
+ *                    "cover_cap_rows") and empties it; cap_rows < 0 gives the
+ *                    pile up.  While a pile is open wk_dtok_emit also takes a
+ *                    block scanned with `extra` (its ranges go to the pile, its
+ *                    records come from the same per-line arrays).
+ *   wk_dtok_cover_append  the ranges of the block wk_dtok_scan parsed last with
+ *                    `extra` (align.parse_sam_file_ex / parse_b6o_file_ex /
+ *                    parse_paf_file_ex + range.range_mapper, range.py:28-86:
+ *                    every mapped line, zero-length ones too), before
+ *                    wk_dtok_emit; WK_E_STATE without such a block.  *n_lines =
+ *                    lines of the block this call went through (the rows are
+ *                    those with a subject: counted on the device, read when
+ *                    room runs out or at wk_cover_finish -- a block's ranges
+ *                    cost no wait of their own).
+ *   wk_cover_add     rows from the host (blocks the host tokenised).
+ *                    *n_taken = rows of the n that were appended.
+ *   Both compact the pile (sort + merge) when its tail has no room.  When the
+ *   merged set alone then fills more than half the pile they stop early --
+ *   *full = 1 / *n_taken < n; nothing is lost: the caller fetches the merged
+ *   set (wk_cover_finish, wk_cover_fetch), empties the pile (wk_cover_reset)
+ *   and repeats the call, which goes on where it stopped; the union of what was
+ *   fetched and what follows is the result.
+ *   wk_cover_finish  compacts; *n_ranges = merged ranges, which stay resident.
+ *   wk_cover_fetch   the merged ranges sorted by (subject, beg); WK_E_CAPACITY
+ *                    when cap < their number, WK_E_STATE before wk_cover_finish.
+ *   wk_cover_reset   empties the pile (it stays open). */
+int wk_cover_begin(wk_ctx* ctx, int64_t cap_rows);
+int wk_dtok_cover_append(wk_ctx* ctx, int64_t* n_lines, int* full);
+int wk_cover_add(wk_ctx* ctx, const int32_t* subj, const int32_t* beg,
+                 const int32_t* end, int64_t n, int64_t* n_taken);
+int wk_cover_finish(wk_ctx* ctx, int64_t* n_ranges);
+int wk_cover_fetch(wk_ctx* ctx, int32_t* subj, int32_t* beg, int32_t* end,
+                   int64_t cap);
+int wk_cover_reset(wk_ctx* ctx);
 
 /* ---- read maps formatted on the device (csrc/wk_readmap.hpp) ----------------
  * file.write_readmap (file.py:469-500) for blocks the device tokenised: the

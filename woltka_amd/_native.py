@@ -57,6 +57,8 @@ SYMBOLS = (
     'wk_dtok_copy_drop', 'wk_dtok_subject_map', 'wk_dtok_ahead_room', 'wk_dtok_text_back', 'wk_dtok_expect', 'wk_dtok_scan', 'wk_dtok_emit', 'wk_dtok_stage_hits', 'wk_dtok_stage_hits_append',
     'wk_dtok_scan_emit', 'wk_dtok_scan_emit_begin', 'wk_dtok_scan_emit_end',
     'wk_dtok_keep_reads', 'wk_readmap_tables',
+    'wk_cover_begin', 'wk_dtok_cover_append', 'wk_cover_add',
+    'wk_cover_finish', 'wk_cover_fetch', 'wk_cover_reset',
     'wk_dtok_readmap',
     'wk_dtok_readmap_fetch', 'wk_strata_load', 'wk_strata_labels',
     'wk_strata_groups', 'wk_strata_clear',
@@ -222,6 +224,12 @@ def load_library():
         'wk_dtok_scan_emit_end': (C.c_int, [p, i64p, C.POINTER(C.c_int), i64p,
                                             i64p]),
         'wk_dtok_keep_reads': (C.c_int, [p, C.c_int]),
+        'wk_cover_begin': (C.c_int, [p, C.c_int64]),
+        'wk_dtok_cover_append': (C.c_int, [p, i64p, C.POINTER(C.c_int)]),
+        'wk_cover_add': (C.c_int, [p, i32p, i32p, i32p, C.c_int64, i64p]),
+        'wk_cover_finish': (C.c_int, [p, i64p]),
+        'wk_cover_fetch': (C.c_int, [p, i32p, i32p, i32p, C.c_int64]),
+        'wk_cover_reset': (C.c_int, [p]),
         'wk_readmap_tables': (C.c_int, [p, C.c_int32, i32p, C.c_int32, i32p,
                                         u32p, C.c_char_p, C.c_int32]),
         'wk_dtok_readmap': (C.c_int, [p, C.c_int32, i64p]),
@@ -776,6 +784,69 @@ class Context:
         self._check(self._lib.wk_dtok_emit(self._h, C.byref(a), C.byref(b),
                                            C.byref(st)))
         return st.value, a.value, b.value
+
+    # -- subject coverage on the device (csrc/wk_cover.hpp) ---------------
+    def cover_begin(self, cap_rows=0):
+        """Reserve and empty the coverage pile (0: the ``cover_cap_rows``
+        option's size; negative: give the pile up)."""
+        self._check(self._lib.wk_cover_begin(self._h, int(cap_rows)))
+
+    def cover_reset(self):
+        self._check(self._lib.wk_cover_reset(self._h))
+
+    def cover_fetch(self):
+        """Compact the pile and return its merged ranges (subject, beg, end),
+        sorted by (subject, beg); they stay on the device."""
+        n = C.c_int64(0)
+        self._check(self._lib.wk_cover_finish(self._h, C.byref(n)))
+        subj, beg, end = (np.empty(n.value, dtype=np.int32) for _ in range(3))
+        self._check(self._lib.wk_cover_fetch(
+            self._h, _ptr(subj, C.c_int32), _ptr(beg, C.c_int32),
+            _ptr(end, C.c_int32), n.value))
+        return subj, beg, end
+
+    def _cover_spill(self, spill):
+        """The pile is full of merged ranges: they go to ``spill(subject, beg,
+        end)`` -- the union is order-independent, whoever merges the pieces in
+        the end gets the same set -- and the pile starts over."""
+        if spill is None:
+            raise OverflowError('coverage pile full of merged ranges and '
+                                'nowhere to spill them')
+        spill(*self.cover_fetch())
+        self.cover_reset()
+
+    def cover_add(self, subj, beg, end, spill=None):
+        """Rows (subject id, beg, end) to the pile.  Returns the number of
+        spills."""
+        subj, beg, end = (_arr(x, np.int32) for x in (subj, beg, end))
+        if not subj.size == beg.size == end.size:
+            raise ValueError('subject, beg and end of different lengths')
+        done, spills = 0, 0
+        while done < subj.size:
+            took = C.c_int64(0)
+            self._check(self._lib.wk_cover_add(
+                self._h, _ptr(subj[done:], C.c_int32),
+                _ptr(beg[done:], C.c_int32), _ptr(end[done:], C.c_int32),
+                subj.size - done, C.byref(took)))
+            done += took.value
+            if done < subj.size:
+                self._cover_spill(spill)
+                spills += 1
+        return spills
+
+    def dtok_cover_append(self, spill=None):
+        """The ranges of the block scanned last (``extra``) to the pile,
+        before ``dtok_emit``.  Returns (lines gone through, spills)."""
+        rows, spills = 0, 0
+        while True:
+            n, full = C.c_int64(0), C.c_int(0)
+            self._check(self._lib.wk_dtok_cover_append(
+                self._h, C.byref(n), C.byref(full)))
+            rows += n.value
+            if not full.value:
+                return rows, spills
+            self._cover_spill(spill)
+            spills += 1
 
     def dtok_keep_reads(self, on):
         """``wk_dtok_emit`` keeps the per-read state of its block for

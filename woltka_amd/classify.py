@@ -30,6 +30,34 @@ from .routes.replay import Replay
 from .routes.words import WordsRoute
 
 
+# subjects met so far beyond which a file under `--outcov` takes the host route:
+# at 100 k subjects the device route measured 0.93 of the host route's time, at
+# 1 M subjects 1.12 (ranges that hardly merge, profiles/outcov_e2e.json);
+# nothing in between was measured
+COVER_MAX_SUBJECTS = 500_000
+
+
+def cover_on_device(fmt, exclude=False, demux=False, strata=False,
+                    outmap=False, part=None, n_jobs_ok=True, n_subjects=0):
+    """Does a file under `--outcov` keep the device text route, its aligned
+    ranges united on the device (csrc/wk_cover.hpp, `_run_dcover`)?  Plain
+    classification of SAM, BLAST tabular or PAF text whose job set the
+    packed records take (``n_jobs_ok``: `Engine.words_eligible`).  Not with
+    `--exclude` (the reference's filtering "ex" parser yields its pool once
+    more at the end of a file whose last query was dropped, align.py:542-547:
+    the host tokenizer tracks that), `--demux`, a strata map, read maps or a
+    byte range of a file; not a simple map (it has no ranges); not once the
+    files before this one have brought more than `COVER_MAX_SUBJECTS`
+    subjects (``n_subjects``: the route was measured slower there; a single
+    file's subjects are not known when its route is chosen).
+    ``WOLTKA_NO_DCOVER=1`` keeps every file on the host route."""
+    if os.environ.get('WOLTKA_NO_DCOVER'):
+        return False
+    return bool(fmt in ('sam', 'b6o', 'paf') and not exclude and not demux
+                and not strata and not outmap and part is None and n_jobs_ok
+                and n_subjects <= COVER_MAX_SUBJECTS)
+
+
 class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
              Folding):
     """One classification job on one GPU.
@@ -152,6 +180,9 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
         self._dexclude = None       # ... and its `--exclude` set
         self._tok_genome = np.empty(0, dtype=np.int32)
         self._tok_cover = np.empty(0, dtype=np.int64)
+        self._dcover = None         # the `Coverage` of the file on the device text route (`--outcov`)
+        self._cv_cover, self._cv_sample = None, None    # whose ranges the device's coverage pile holds
+        self._cv_open = False
         self._ring, self._ring_prev = None, None    # packed-record staging
         self._oring = None                          # coord-match staging
         self._tring, self._reader = None, None      # device tokenizer: text staging, reader threads
@@ -329,14 +360,17 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
                       want_names, trimsub=None, want_groups=False,
                       want_strings=True, want_samples=False, cover=None,
                       fmt='sam', part=None, words=False, dmaps=None,
-                      keep_empty=False, words_dev=False):
+                      keep_empty=False, words_dev=False, dcover=False):
         """SAM text -> packed chunks through the native tokenizer.  Yields
         (reads or None, packed, strata ids, name descriptors, sample ids,
         ranges) where packed = (subj, qoff) of subject indices, or for
         coord-match (genome, beg, end, length, hoff).  With ``cover`` (a
         ``ranges.Coverage``) the "ex" columns are produced for plain
         classification too and ``ranges`` = (coverage subject id, beg, end) per
-        record.  ``keep_empty``: hits of aligned length 0 stay in the arrays
+        record -- or, with ``dcover`` (`cover_on_device`), the ranges stay on
+        the device: the blocks' union is fetched into ``cover`` when the
+        sample changes and at the end (`cover_flush`).
+        ``keep_empty``: hits of aligned length 0 stay in the arrays
         (`regroup_hits` counts them where ordinal.py:222 does, then drops
         them)."""
         from .align import native_sam_blocks
@@ -360,7 +394,8 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
         # are not the subjects and the kernels translate)
         # (`--exclude`: the plain flavour's kernels drop the runs that hit a
         # name of the set; not with read maps, not the "ex" parsers' way)
-        if (words or words_dev or device_ex or dmaps) and (
+        dcover = bool(dcover and cover is not None and not ordinal)
+        if (words or words_dev or device_ex or dmaps or dcover) and (
                 fmt in ('sam', 'b6o', 'paf') or (fmt == 'map' and
                                                  not ordinal)) and \
                 (not exclude or ((words or words_dev) and not dmaps)) and \
@@ -385,7 +420,9 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
             if reader is not None:
                 # the text goes to the GPU as it is: tokenised there (with
                 # `dmaps` the read maps are formatted there too)
-                self._dmaps = dmaps if not (words or device_ex) else None
+                self._dmaps = dmaps if not (words or device_ex or dcover) \
+                    else None
+                self._dcover = cover if dcover else None
                 self.ctx.dtok_keep_reads(self._dmaps is not None)
                 self._dfmt = fmt
                 self._dtrimsub = trimsub if not ordinal else None
@@ -403,9 +440,11 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
                 self.ctx.dtok_format(fmt)
                 try:
                     yield from self._device_chunks(reader, block_bytes,
-                                                   ordinal=bool(ordinal))
+                                                   ordinal=bool(ordinal),
+                                                   cover=dcover)
                 finally:
                     self._dmaps = None
+                    self._dcover = None
                     if getattr(self.ctx, '_h', None):   # (still open)
                         self.ctx.dtok_keep_reads(False)
                 return
@@ -632,6 +671,7 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
 
     # route of a chunk by the tag of its `packed` tuple
     ROUTE_OF = {'dtok': '_run_dtok',        # text scanned on the device -> packed records (routes/device_text.py)
+                'dcover': '_run_dcover',    # ... for the "ex" parsers under `--outcov`: ranges to the coverage pile, then the same
                 'dhits': '_run_dhits',      # text scanned on the device -> coord-match hits
                 'words': '_run_words'}      # packed records of the host tokenizer (routes/words.py)
 

@@ -20,6 +20,7 @@
 #include "../../include/woltka_hip.h"
 #include "../../include/woltka_hip_measure.h"
 #include "wk_classify.hpp"
+#include "wk_cover.hpp"
 #include "wk_device.hpp"
 #include "wk_dtok.hpp"
 #include "wk_dtok_fused.hpp"
@@ -325,6 +326,19 @@ struct wk_ctx {
     uint32_t dt_submap_n = 0;     // wk_dtok_subject_map (0: the tokenizer's ids are the subject indices)
     DevBuf d_lbeg, d_lend, d_llen, d_lscan, d_gmap;  // "ex" flavour
     bool dt_extra = false;
+    // coverage pile (wk_cover.hpp): two buffers of rows (the sort's ping-pong; cv_cur holds the pile), the merged set
+    // of the sample so far in front of the rows appended since
+    DevBuf cv_key[2], cv_end[2], cv_reach, cv_hist, cv_tiles, cv_tile_off, cv_state, cv_stage[3];
+    bool cv_open = false;
+    int cv_cur = 0;
+    int64_t cv_cap = 0;       // rows a buffer holds
+    int64_t cv_cap_opt = 0;   // wk_set_option("cover_cap_rows"): what wk_cover_begin(ctx, 0) reserves (0: kCoverCapDefault)
+    int64_t cv_tail = 0;      // rows in the pile, the merged set included
+    int64_t cv_merged = 0;    // rows of the merged set
+    int64_t cv_ub = 0;        // upper bound of the tail: cv_tail + the lines handed to cover_append since it was read
+    bool cv_stale = false;    // rows have been appended since cv_tail / cv_seen were read
+    CoverState cv_seen{};     // the device's scalars as read last
+    uint32_t cv_line_next = 0;  // lines of the block scanned last that wk_dtok_cover_append has been through
     // measurement (woltka_hip_measure.h): blocks of text that are resident on the device already
     // (wk_text_upload) -- the scan of such a block copies nothing
     struct ResidentText {
@@ -1042,7 +1056,8 @@ void wk_destroy(wk_ctx* c) {
         if (q % wk_ctx::kSlabBufs == 0) c->d_textslab[q / wk_ctx::kSlabBufs].release();
     }
     for (DevBuf* b : {&c->d_tiles, &c->d_tile_off, &c->d_lines, &c->d_lsubj, &c->d_lmeta, &c->d_start, &c->d_first, &c->d_unknown, &c->d_lbeg, &c->d_lend, &c->d_llen, &c->d_lscan, &c->d_gmap,
-                      &c->d_state, &c->d_dict, &c->d_dict2, &c->d_names16, &c->d_arena, &c->d_submap})
+                      &c->d_state, &c->d_dict, &c->d_dict2, &c->d_names16, &c->d_arena, &c->d_submap, &c->cv_key[0], &c->cv_key[1], &c->cv_end[0], &c->cv_end[1],
+                      &c->cv_reach, &c->cv_hist, &c->cv_tiles, &c->cv_tile_off, &c->cv_state, &c->cv_stage[0], &c->cv_stage[1], &c->cv_stage[2]})
         b->release();
     for (wk_ctx::ResidentText& r : c->resident) {
         (void)hipFree(r.dev);
@@ -1096,6 +1111,12 @@ int wk_set_option(wk_ctx* c, const char* name, int64_t value) {
     }
     if (!strcmp(name, "dtok_count_ahead")) {  // 0: no newline count behind the copies of blocks (wk_dtok_copy*): the scans count the blocks that need it
         c->count_ahead = value != 0;
+        return WK_OK;
+    }
+    if (!strcmp(name, "cover_cap_rows")) {  // rows of the coverage pile that wk_cover_begin(ctx, 0) reserves (0: the default); results never depend on it
+        if (value != 0 && (value < kCoverCapMin || value > kCoverCapMax))
+            return fail(c, WK_E_ARG, "cover_cap_rows must be 0 or in [%lld, %lld]", (long long)kCoverCapMin, (long long)kCoverCapMax);
+        c->cv_cap_opt = value;
         return WK_OK;
     }
     return fail(c, WK_E_ARG, "unknown option '%s' (launch shapes and ablation switches: wk_tune)", name);
@@ -3082,6 +3103,7 @@ static int dtok_scan_impl(wk_ctx* c, wk_tok* tok, const char* text, int64_t begi
     *n_lines = 0;
     c->dt_ready = false;
     c->dt_extra = extra != 0;
+    c->cv_line_next = 0;
     // (an exclusion set: the plain flavour takes it as kLineExcluded entries of the subject map, wk_dtok_subject_map;
     // the "ex" parsers' way with it -- align.py:481-547 yields a stale pool at the end of a file -- stays the host's)
     if (!wkx_tok_device_ok(tok) && (extra || !c->dt_submap_on)) return WK_OK;
@@ -3783,7 +3805,9 @@ int wk_dtok_emit(wk_ctx* c, int64_t* n_reads, int64_t* n_records, int* status) {
     if (!c || !n_reads || !n_records || !status) return WK_E_ARG;
     *status = 1;
     *n_reads = *n_records = 0;
-    if (!c->dt_ready || c->dt_extra) return fail(c, WK_E_STATE, "no block scanned for the plain flavour (wk_dtok_scan)");
+    // (an "ex" block while a coverage pile is open: its ranges went to the pile, wk_dtok_cover_append; its lines' subjects,
+    // query lengths and mates are what the plain parse leaves, so the records come from the same kernels)
+    if (!c->dt_ready || (c->dt_extra && !c->cv_open)) return fail(c, WK_E_STATE, "no block scanned for the plain flavour (wk_dtok_scan)");
     if (!c->w_open) return fail(c, WK_E_STATE, "wk_words_begin has not accepted a job set");
     c->dt_ready = false;
     if (c->dt_lines == 0) {
@@ -3804,6 +3828,267 @@ int wk_dtok_emit(wk_ctx* c, int64_t* n_reads, int64_t* n_records, int* status) {
     // (a read of more than 16 subjects: nothing counts as appended)
     if ((rc = dtok_emit_finish(c, st.flags == 0, ordered, st, totals, n_reads, n_records))) return rc;
     if (st.flags == 0) *status = 0;
+    return WK_OK;
+}
+
+// ---- subject coverage on the device (wk_cover.hpp) ------------------------------------------------------------------
+
+// the pile's scalars (after everything queued so far)
+static int cover_read_state(wk_ctx* c) {
+    static_assert(sizeof(CoverState) <= (size_t)wk_ctx::kBackBytes && sizeof(CoverState) % 4 == 0, "CoverState fits a slot");
+    HIP_TRY(c, small_back(c, 1, c->cv_state.p, sizeof(CoverState)));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    small_back_get(c, 1, &c->cv_seen, sizeof(CoverState));
+    if (c->cv_seen.overflow || c->cv_seen.tail > (unsigned long long)c->cv_cap)
+        return fail(c, WK_E_STATE, "coverage pile: rows beyond the room reserved for them");
+    c->cv_tail = c->cv_ub = (int64_t)c->cv_seen.tail;
+    c->cv_stale = false;
+    return WK_OK;
+}
+
+// The exact tail is wanted when room runs out, not behind every append: until then cv_ub (every line handed over counted
+// as a row) stands in for it, and a block's ranges cost no wait of their own.
+static int cover_sync(wk_ctx* c) { return c->cv_stale ? cover_read_state(c) : WK_OK; }
+
+static int cover_clear(wk_ctx* c) {
+    CoverState st{};
+    st.key_and = ~0ull;
+    st.end_and = ~0u;
+    HIP_TRY(c, hipMemcpyAsync(c->cv_state.p, &st, sizeof st, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->cv_seen = st;
+    c->cv_tail = c->cv_merged = c->cv_ub = 0;
+    c->cv_stale = false;
+    c->cv_cur = 0;
+    return WK_OK;
+}
+
+// Sort the pile and merge it: the merged set is the pile afterwards (in the other buffer of the sorted rows).
+static int cover_compact(wk_ctx* c) {
+    int rc = cover_sync(c);
+    if (rc) return rc;
+    if (c->cv_tail == c->cv_merged) return WK_OK;  // (nothing behind the merged set)
+    const uint32_t n = (uint32_t)c->cv_tail;
+    KernelTimer* kt = ktimer_begin(c, "cover_sort");
+    // the digits that differ between rows: of `end` first when rows with end < beg are about (a sort by (subject, beg,
+    // end) then, as merge_ranges'), then of the key
+    const uint32_t n_chunks = (n + kCoverChunk - 1) / kCoverChunk;
+    const uint32_t n_matrix = 256u * n_chunks;
+    const uint32_t n_mtiles = (n_matrix + kCoverTile - 1) / kCoverTile;
+    int cur = c->cv_cur;
+    auto pass = [&](uint32_t from_end, uint32_t shift) {
+        CoverSortArgs a{};
+        a.key_in = c->cv_key[cur].as<unsigned long long>();
+        a.end_in = c->cv_end[cur].as<int32_t>();
+        a.key_out = c->cv_key[cur ^ 1].as<unsigned long long>();
+        a.end_out = c->cv_end[cur ^ 1].as<int32_t>();
+        a.n = n;
+        a.n_chunks = n_chunks;
+        a.shift = shift;
+        a.from_end = from_end;
+        a.hist = c->cv_hist.as<uint32_t>();
+        a.st = c->cv_state.as<CoverState>();
+        const dim3 grid((n_chunks + kCoverWaves - 1) / kCoverWaves);
+        hipLaunchKernelGGL(cover_hist_kernel, grid, dim3(kCoverThreads), 0, c->stream, a);
+        hipLaunchKernelGGL(cover_sum_tiles_kernel, dim3(n_mtiles), dim3(kCoverThreads), 0, c->stream, (const uint32_t*)a.hist, n_matrix,
+                           c->cv_tiles.as<unsigned long long>());
+        hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, c->stream, c->cv_tiles.as<unsigned long long>(),
+                           c->cv_tile_off.as<unsigned long long>(), (int64_t)n_mtiles, scalar_u64(c, 3));
+        hipLaunchKernelGGL(cover_scan_apply_kernel, dim3(n_mtiles), dim3(kCoverThreads), 0, c->stream, a.hist, n_matrix,
+                           (const unsigned long long*)c->cv_tile_off.as<unsigned long long>());
+        hipLaunchKernelGGL(cover_scatter_kernel, grid, dim3(kCoverThreads), 0, c->stream, a);
+        cur ^= 1;
+    };
+    const uint32_t end_diff = c->cv_seen.end_or ^ c->cv_seen.end_and;
+    const unsigned long long key_diff = c->cv_seen.key_or ^ c->cv_seen.key_and;
+    if (c->cv_seen.degenerate)
+        for (uint32_t b = 0; b < 4; ++b)
+            if ((end_diff >> (8 * b)) & 255u) pass(1, 8 * b);
+    for (uint32_t b = 0; b < 8; ++b)
+        if ((key_diff >> (8 * b)) & 255ull) pass(0, 8 * b);
+    ktimer_end(c, kt);
+    HIP_TRY(c, hipGetLastError());
+    kt = ktimer_begin(c, "cover_merge");
+    const uint32_t n_tiles = (n + kCoverTile - 1) / kCoverTile;
+    CoverMergeArgs m{};
+    m.key = c->cv_key[cur].as<unsigned long long>();
+    m.end = c->cv_end[cur].as<int32_t>();
+    m.n = n;
+    m.reach = c->cv_reach.as<int32_t>();
+    m.tile_max = c->cv_tiles.as<unsigned long long>();
+    m.tile_heads = c->cv_tiles.as<unsigned long long>() + n_tiles;
+    m.tile_off = c->cv_tile_off.as<unsigned long long>();
+    m.key_out = c->cv_key[cur ^ 1].as<unsigned long long>();
+    m.end_out = c->cv_end[cur ^ 1].as<int32_t>();
+    hipLaunchKernelGGL(cover_max_tiles_kernel, dim3(n_tiles), dim3(kCoverThreads), 0, c->stream, m);
+    hipLaunchKernelGGL(cover_max_scan_kernel, dim3(1), dim3(1024), 0, c->stream, m.tile_max, n_tiles);
+    hipLaunchKernelGGL(cover_reach_kernel, dim3(n_tiles), dim3(kCoverThreads), 0, c->stream, m);
+    hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, c->stream, m.tile_heads, c->cv_tile_off.as<unsigned long long>(),
+                       (int64_t)n_tiles, scalar_u64(c, 3));
+    hipLaunchKernelGGL(cover_compact_kernel, dim3(n_tiles), dim3(kCoverThreads), 0, c->stream, m);
+    hipLaunchKernelGGL(cover_set_tail_kernel, dim3(1), dim3(1), 0, c->stream, c->cv_state.as<CoverState>(),
+                       (const unsigned long long*)scalar_u64(c, 3));
+    ktimer_end(c, kt);
+    HIP_TRY(c, hipGetLastError());
+    c->cv_cur = cur ^ 1;
+    if ((rc = cover_read_state(c))) return rc;
+    if (c->cv_tail > (int64_t)n) return fail(c, WK_E_STATE, "coverage pile: more merged ranges than rows");
+    c->cv_merged = c->cv_tail;
+    return WK_OK;
+}
+
+// Room for up to `want` more rows: how many of them may be appended now (0: the merged set alone fills more than half the
+// pile -- the caller fetches it, resets and comes back).  Compacts when the tail has no room for them.
+static int cover_room(wk_ctx* c, int64_t want, int64_t* room) {
+    *room = c->cv_cap - c->cv_ub;
+    if (*room >= want) return WK_OK;
+    int rc = cover_sync(c);  // (the bound says no: the exact tail may say yes)
+    if (rc) return rc;
+    *room = c->cv_cap - c->cv_tail;
+    if (*room >= want) return WK_OK;
+    if (*room < c->cv_cap / 4) {
+        if ((rc = cover_compact(c))) return rc;
+        *room = c->cv_merged > c->cv_cap / 2 ? 0 : c->cv_cap - c->cv_tail;
+    }
+    return WK_OK;
+}
+
+static void cover_append_launch(wk_ctx* c, const int32_t* subj, const int32_t* beg, const int32_t* end, uint32_t i0, uint32_t i1) {
+    hipLaunchKernelGGL(cover_append_kernel, dim3((i1 - i0 + kCoverThreads - 1) / kCoverThreads), dim3(kCoverThreads), 0, c->stream, subj, beg, end,
+                       i0, i1, c->cv_key[c->cv_cur].as<unsigned long long>(), c->cv_end[c->cv_cur].as<int32_t>(), (unsigned long long)c->cv_cap,
+                       c->cv_state.as<CoverState>());
+}
+
+int wk_cover_begin(wk_ctx* c, int64_t cap_rows) {
+    if (!c) return WK_E_ARG;
+    DeviceGuard guard(c->device);
+    if (cap_rows < 0) {  // the pile is given up
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        for (DevBuf* b : {&c->cv_key[0], &c->cv_key[1], &c->cv_end[0], &c->cv_end[1], &c->cv_reach, &c->cv_hist, &c->cv_tiles, &c->cv_tile_off,
+                          &c->cv_stage[0], &c->cv_stage[1], &c->cv_stage[2]})
+            b->release();
+        c->cv_open = false;
+        c->cv_cap = c->cv_tail = c->cv_merged = c->cv_ub = 0;
+        c->cv_stale = false;
+        return WK_OK;
+    }
+    if (cap_rows == 0) cap_rows = c->cv_cap_opt ? c->cv_cap_opt : kCoverCapDefault;
+    if (cap_rows < kCoverCapMin || cap_rows > kCoverCapMax)
+        return fail(c, WK_E_ARG, "a coverage pile holds %lld to %lld rows", (long long)kCoverCapMin, (long long)kCoverCapMax);
+    // (the merge's threads load whole tiles: the buffers end at a tile's end)
+    const size_t rows = ((size_t)cap_rows + kCoverTile - 1) / kCoverTile * kCoverTile;
+    const size_t n_chunks = ((size_t)cap_rows + kCoverChunk - 1) / kCoverChunk;
+    const size_t n_mtiles = (256 * n_chunks + kCoverTile - 1) / kCoverTile;
+    const size_t n_tiles = rows / kCoverTile;
+    for (int k = 0; k < 2; ++k) {
+        HIP_TRY(c, c->cv_key[k].reserve(rows * 8));
+        HIP_TRY(c, c->cv_end[k].reserve(rows * 4));
+    }
+    HIP_TRY(c, c->cv_reach.reserve(rows * 4));
+    HIP_TRY(c, c->cv_hist.reserve(256 * n_chunks * 4));
+    HIP_TRY(c, c->cv_tiles.reserve(std::max(n_mtiles, 2 * n_tiles) * 8));
+    HIP_TRY(c, c->cv_tile_off.reserve(std::max(n_mtiles, n_tiles) * 8));
+    HIP_TRY(c, c->cv_state.reserve(sizeof(CoverState)));
+    c->cv_cap = cap_rows;
+    c->cv_open = true;
+    return cover_clear(c);
+}
+
+int wk_cover_reset(wk_ctx* c) {
+    if (!c) return WK_E_ARG;
+    if (!c->cv_open) return fail(c, WK_E_STATE, "no coverage pile (wk_cover_begin)");
+    DeviceGuard guard(c->device);
+    return cover_clear(c);
+}
+
+int wk_cover_add(wk_ctx* c, const int32_t* subj, const int32_t* beg, const int32_t* end, int64_t n, int64_t* n_taken) {
+    if (!c || n < 0 || !n_taken || (n > 0 && (!subj || !beg || !end))) return WK_E_ARG;
+    *n_taken = 0;
+    if (!c->cv_open) return fail(c, WK_E_STATE, "no coverage pile (wk_cover_begin)");
+    DeviceGuard guard(c->device);
+    KtScope kt_scope(c);
+    while (*n_taken < n) {
+        int64_t room = 0;
+        int rc = cover_room(c, n - *n_taken, &room);
+        if (rc) return rc;
+        if (room == 0) return WK_OK;  // (*n_taken < n: the pile is full of merged ranges)
+        const int64_t take = std::min(room, n - *n_taken);
+        const int32_t* src[3] = {subj + *n_taken, beg + *n_taken, end + *n_taken};
+        for (int k = 0; k < 3; ++k)
+            if ((rc = upload(c, c->cv_stage[k], src[k], (size_t)take * 4))) return rc;
+        KernelTimer* kt = ktimer_begin(c, "cover_append");
+        cover_append_launch(c, c->cv_stage[0].as<int32_t>(), c->cv_stage[1].as<int32_t>(), c->cv_stage[2].as<int32_t>(), 0u, (uint32_t)take);
+        ktimer_end(c, kt);
+        HIP_TRY(c, hipGetLastError());
+        // (the staged rows are read by the kernel: waited for before the next piece overwrites them)
+        if ((rc = cover_read_state(c))) return rc;
+        *n_taken += take;
+    }
+    return WK_OK;
+}
+
+// The ranges of the block scanned last ("ex" flavour) -> the pile: every line with a subject (the tokenizer's id: coverage
+// is keyed by the name in the file).  *full = 1: the pile is full of merged ranges and lines of the block are left --
+// after wk_cover_fetch + wk_cover_reset the same call goes on where it stopped.
+int wk_dtok_cover_append(wk_ctx* c, int64_t* n_lines, int* full) {
+    if (!c || !n_lines || !full) return WK_E_ARG;
+    *n_lines = 0;
+    *full = 0;
+    if (!c->cv_open) return fail(c, WK_E_STATE, "no coverage pile (wk_cover_begin)");
+    if (!c->dt_ready || !c->dt_extra) return fail(c, WK_E_STATE, "no block scanned for the \"ex\" flavour (wk_dtok_scan)");
+    if (c->dt_mapped) return fail(c, WK_E_STATE, "the block's subjects have been translated already (wk_dtok_emit)");
+    DeviceGuard guard(c->device);
+    KtScope kt_scope(c);
+    while (c->cv_line_next < c->dt_lines) {
+        const int64_t left = (int64_t)c->dt_lines - c->cv_line_next;
+        int64_t room = 0;
+        int rc = cover_room(c, left, &room);
+        if (rc) return rc;
+        if (room == 0) {
+            *full = 1;
+            break;
+        }
+        const uint32_t take = (uint32_t)std::min(room, left);
+        KernelTimer* kt = ktimer_begin(c, "cover_append");
+        cover_append_launch(c, c->d_lsubj.as<int32_t>(), c->d_lbeg.as<int32_t>(), c->d_lend.as<int32_t>(), c->cv_line_next, c->cv_line_next + take);
+        ktimer_end(c, kt);
+        HIP_TRY(c, hipGetLastError());
+        c->cv_ub += take;
+        c->cv_stale = true;
+        c->cv_line_next += take;
+        *n_lines += take;
+    }
+    return WK_OK;
+}
+
+int wk_cover_finish(wk_ctx* c, int64_t* n_ranges) {
+    if (!c || !n_ranges) return WK_E_ARG;
+    *n_ranges = 0;
+    if (!c->cv_open) return fail(c, WK_E_STATE, "no coverage pile (wk_cover_begin)");
+    DeviceGuard guard(c->device);
+    KtScope kt_scope(c);
+    const int rc = cover_compact(c);
+    if (rc) return rc;
+    *n_ranges = c->cv_merged;
+    return WK_OK;
+}
+
+int wk_cover_fetch(wk_ctx* c, int32_t* subj, int32_t* beg, int32_t* end, int64_t cap) {
+    if (!c || cap < 0 || (cap > 0 && (!subj || !beg || !end))) return WK_E_ARG;
+    if (!c->cv_open) return fail(c, WK_E_STATE, "no coverage pile (wk_cover_begin)");
+    if (c->cv_stale || c->cv_tail != c->cv_merged) return fail(c, WK_E_STATE, "rows behind the merged set (wk_cover_finish)");
+    const int64_t n = c->cv_merged;
+    if (n > cap) return fail(c, WK_E_CAPACITY, "need room for %lld merged ranges", (long long)n);
+    if (n == 0) return WK_OK;
+    DeviceGuard guard(c->device);
+    std::vector<unsigned long long> keys((size_t)n);
+    HIP_TRY(c, hipMemcpyAsync(keys.data(), c->cv_key[c->cv_cur].p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(end, c->cv_end[c->cv_cur].p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int64_t i = 0; i < n; ++i) {
+        subj[i] = (int32_t)(keys[(size_t)i] >> 32);
+        beg[i] = (int32_t)((uint32_t)keys[(size_t)i] ^ kCoverBias);
+    }
     return WK_OK;
 }
 

@@ -66,7 +66,11 @@ def merge_intervals(key, beg, end):
     head[1:] |= beg[1:] > reach[:-1]
     first = np.flatnonzero(head)
     last = np.append(first[1:] - 1, key.size - 1)
-    return key[first], beg[first], reach[last]
+    # (a head with end < beg stands alone -- nothing starts at or before its
+    # end -- and keeps its own end: range.py:112-120 starts every new range
+    # from the row's end, not from the running maximum)
+    return key[first], beg[first], np.where(end[first] < beg[first],
+                                            end[first], reach[last])
 
 
 class Coverage:

@@ -665,6 +665,7 @@ class DeviceTextRoute:
                                                   False)
 
     DTOK_BLOCK = int(os.environ.get('WOLTKA_DTOK_BLOCK', 1 << 26))
+    COVER_CAP_ROWS = 0      # rows of the coverage pile on the device (0: the library's default); results never depend on it
     DTOK_READ_PIECE = int(os.environ.get('WOLTKA_READ_PIECE', 8 << 20))   # bytes per pread of the block reader's threads
     DTOK_AHEAD = int(os.environ.get('WOLTKA_TEXT_AHEAD', 160))     # blocks copied to the device ahead of the one being scanned (at most wk_ctx::kTextBufs - 1) by the reader that starts before the hierarchy is read
     DTOK_DEPTH = int(os.environ.get('WOLTKA_TEXT_DEPTH', 6))       # ... by a reader the engine starts when a file's turn comes: the scans follow at once, a deeper queue only takes the CPUs from whoever else works (config 5's second call: 2.11 s with 3, 2.17 with 160, tools/ab_text_ahead.sh)
@@ -673,7 +674,7 @@ class DeviceTextRoute:
     HOSTREG_MIN = 64 << 20      # smaller files are read into pinned buffers
     HOSTREG_RATE = 40e9         # bytes/s of the first piece's pinning below which the file is read instead
 
-    def _device_chunks(self, reader, host_block, ordinal=False):
+    def _device_chunks(self, reader, host_block, ordinal=False, cover=False):
         """A SAM file through the tokenizer on the device (csrc/wk_dtok.hpp):
         a helper thread reads blocks into pinned buffers (pread by its own
         threads) and cuts them where the last run of equal query ids starts;
@@ -681,7 +682,11 @@ class DeviceTextRoute:
         subjects the block brought are registered — group and append them.
         Blocks the kernels leave to the host tokenizer (malformed lines, both
         mate bits, reads of more than 16 subjects) are tokenised on the host
-        as before.  Yields what `native_chunks` yields."""
+        as before.  Yields what `native_chunks` yields.  ``cover``: plain
+        classification with subject coverage -- the blocks are cut and
+        scanned for the "ex" parsers, their ranges go to the coverage pile on
+        the device and their records the plain flavour's way (`_run_dcover`)."""
+        ex = bool(ordinal or cover)     # cut and scanned for the "ex" parsers
         source = None               # a stream (inflated text) instead of a file
         start = 0                   # (a byte range of a file: [start, size))
         if isinstance(reader, tuple):
@@ -695,8 +700,7 @@ class DeviceTextRoute:
         taken = None
         if _text_ahead:
             if source is None and self._tring is None:
-                taken = take_text_ahead(self._dpath, self._dfmt, self.ctx,
-                                        ordinal)
+                taken = take_text_ahead(self._dpath, self._dfmt, self.ctx, ex)
             else:
                 drop_text_ahead()
         if taken is not None:
@@ -809,7 +813,7 @@ class DeviceTextRoute:
                     fill_n = out.size
                     t0 = time.perf_counter()
                     ok, begin, stop, hdr = nat.Tokenizer.sam_span(
-                        out, final, in_header, self._dfmt, ordinal)
+                        out, final, in_header, self._dfmt, ex)
                     lap['span'] += time.perf_counter() - t0
                     if not ok and not final:    # no complete run yet: read more
                         carry = out.tobytes()
@@ -872,8 +876,7 @@ class DeviceTextRoute:
                 t0 = time.perf_counter()
                 ok, begin, stop, hdr = nat.Tokenizer.sam_span(view, final,
                                                               in_header,
-                                                              self._dfmt,
-                                                              ordinal)
+                                                              self._dfmt, ex)
                 lap['span'] += time.perf_counter() - t0
                 if (not ok or stop == 0) and not final:
                     # no complete run yet -- or one run from the view's first
@@ -956,14 +959,14 @@ class DeviceTextRoute:
             try:
                 t0 = time.perf_counter()
                 done = None
-                if self._spec and not ordinal:
+                if self._spec and not ex:
                     # (the sample's words are open and the block before went
                     # through: scan and emission with one wait)
                     status, n_lines, done = self.ctx.dtok_scan_emit(
                         tok, buf, begin, stop)
                 else:
                     status, n_lines = self.ctx.dtok_scan(tok, buf, begin, stop,
-                                                         extra=ordinal)
+                                                         extra=ex)
                 lap['scan'] += time.perf_counter() - t0
                 lap['blocks'] += 1
                 t1 = time.perf_counter()
@@ -992,6 +995,8 @@ class DeviceTextRoute:
                     return
                 if fresh:
                     self._map_fresh(fresh)
+                    if cover:
+                        self._cover_fresh(fresh)
                 if not self._tok_identity and \
                         self._tok_map_sent != self._tok_map.size:
                     # names that are not subjects (`--trim-sub`: several
@@ -1000,15 +1005,16 @@ class DeviceTextRoute:
                     self._tok_map_sent = self._tok_map.size
                 if status == 0:
                     if n_lines:
-                        yield None, ('dtok', (text, fill, first, final, hdr_in,
-                                              hdr, done)), None, None, None, \
-                            None
+                        yield None, ('dcover' if cover else 'dtok', (
+                            text, fill, first, final, hdr_in, hdr, done)), \
+                            None, None, None, None
                     tok.set_header_state(hdr)
                 else:
                     self._spec = False
                     yield from self._host_block(text, fill, first, final,
                                                 hdr_in,
-                                                names=self._dmaps is not None)
+                                                names=self._dmaps is not None,
+                                                cover=cover)
             finally:
                 # (a block in a ring buffer: the reader took the buffer back
                 # when its copy was through)
@@ -1028,7 +1034,7 @@ class DeviceTextRoute:
             # (plain SAM records for the weighted histogram go through the
             # one-kernel tokenizer: no newline count behind a block's copy)
             self.ctx.set_option('dtok_count_ahead', int(bool(
-                ordinal or self._dmaps is not None or self._dfmt != 'sam')))
+                ex or self._dmaps is not None or self._dfmt != 'sam')))
         ahead, whole = taken, None
         if ahead is None:
             whole = open_mapped() if source is None else None
@@ -1044,7 +1050,7 @@ class DeviceTextRoute:
                 gen = text_blocks(ring, self._read_pool, rd, fd, size,
                                   self._dfmt, tok, lap, block,
                                   self.DTOK_HEADROOM, self.DTOK_READ_PIECE,
-                                  extra=ordinal, start=start)
+                                  extra=ex, start=start)
             ahead = _TextAhead(self.ctx, gen, ring,
                                3 if whole is not None else self.DTOK_DEPTH,
                                lap)
@@ -1058,7 +1064,7 @@ class DeviceTextRoute:
         # between.  `lag`: the blocks under way, oldest first.
         from collections import deque
         lag = deque()
-        may_lag = not ordinal and not os.environ.get('WOLTKA_NO_LAG')
+        may_lag = not ex and not os.environ.get('WOLTKA_NO_LAG')
 
         def settle(leave):
             """Read verdicts until `leave` blocks are under way.  A block the
@@ -1189,11 +1195,21 @@ class DeviceTextRoute:
             self._tok_identity = False
         self._tok_map = np.concatenate([self._tok_map, ids])
 
+    def _cover_fresh(self, fresh):
+        """Names the tokenizer has met for the first time -> the coverage's
+        subject ids (coverage is keyed by the name in the file, before
+        `--trim-sub`)."""
+        self._tok_cover = np.concatenate([
+            self._tok_cover,
+            np.fromiter(map(self._dcover.subject, fresh), np.int64,
+                        len(fresh))])
+
     def _host_block(self, buf, fill, first, final, hdr_in, ordinal=False,
-                    names=False, groups=False):
+                    names=False, groups=False, cover=False):
         """One block of the device route through the host tokenizer after
         all (the general arrays; ``names``: with the descriptors of the query
-        names, for the read maps)."""
+        names, for the read maps; ``cover``: the "ex" parsers' records with
+        their ranges (coverage subject id, beg, end) as the last item)."""
         ROUTES['host_block'] += 1
         if isinstance(buf, _BlockText):     # (the bytes come back from the device)
             buf = buf.get()
@@ -1225,15 +1241,20 @@ class DeviceTextRoute:
                     None, None, None
             return
         res = tok.parse(memoryview(buf).cast('B')[:fill], first=first,
-                        final=final, fmt=self._dfmt, want_names=names)
+                        final=final, fmt=self._dfmt, want_names=names,
+                        extra=3 if cover else False)
         fresh = tok.new_subjects()
         if fresh:
             self._map_fresh(fresh)
+            if cover:
+                self._cover_fresh(fresh)
         if res['off'].size > 1:
             subj = res['subj'] if self._tok_identity \
                 else self._tok_map[res['subj']]
             yield None, (subj, res['off']), None, \
-                ((buf[:fill], res['qname']) if names else None), None, None
+                ((buf[:fill], res['qname']) if names else None), None, \
+                ((self._tok_cover[res['subj']], res['beg'], res['end'])
+                 if cover else None)
 
     def _run_dhits(self, data, packed, sample):
         """A block the device has scanned for the coord-match: its hits are
@@ -1295,7 +1316,49 @@ class DeviceTextRoute:
         self.tok.set_header_state(hdr)
         return n
 
-    def _run_dtok(self, data, packed, sample):
+    def cover_flush(self, close=False):
+        """The coverage pile on the device -- one sample's -- into the host
+        `Coverage` (whose `merged()` unites it with whatever the host route
+        and spills added: the union does not depend on the order).
+        ``close``: the pass is over -- the pile is given up (its memory, and
+        `wk_dtok_emit` refuses an "ex" block again)."""
+        cover, self._cv_cover = self._cv_cover, None
+        if cover is None:
+            if close and self._cv_open:
+                self.ctx.cover_begin(-1)
+                self._cv_open = False
+            return
+        subj, beg, end = self.ctx.cover_fetch()
+        if subj.size:
+            cover.add(cover.sample(self._cv_sample), self._tok_cover[subj],
+                      beg, end)
+        if close:
+            self.ctx.cover_begin(-1)
+            self._cv_open = False
+        else:
+            self.ctx.cover_reset()
+        ROUTES['dcover_flush'] += 1
+
+    def _run_dcover(self, data, packed, sample):
+        """A block the device has scanned for the "ex" parsers under
+        `--outcov`: its ranges go to the coverage pile (`wk_dtok_cover_append`,
+        csrc/wk_cover.hpp), its records the way of `_run_dtok`."""
+        cover = self._dcover
+        if self._cv_cover is not None and (self._cv_cover is not cover or
+                                           self._cv_sample != sample):
+            self.cover_flush()
+        if not self._cv_open:
+            self.ctx.set_option('cover_cap_rows', self.COVER_CAP_ROWS)
+            self.ctx.cover_begin(0)
+            self._cv_open = True
+        self._cv_cover, self._cv_sample = cover, sample
+        who = cover.sample(sample)
+        _, spills = self.ctx.dtok_cover_append(
+            lambda s, b, e: cover.add(who, self._tok_cover[s], b, e))
+        ROUTES['dcover_spill'] += spills
+        return self._run_dtok(data, packed, sample, cover=True)
+
+    def _run_dtok(self, data, packed, sample, cover=False):
         """A block the device has scanned: register the subjects it brought,
         have the job set accepted for them, then group and append its records
         (`wk_dtok_emit`).  If the weighted histogram cannot take the block —
@@ -1333,20 +1396,25 @@ class DeviceTextRoute:
             t3 = time.perf_counter()
             lap['emit'] = lap.get('emit', 0.0) + t3 - t2
             if status == 0:
-                ROUTES['dtok_maps' if dmaps is not None else 'dtok'] += 1
+                ROUTES['dcover' if cover else
+                       'dtok_maps' if dmaps is not None else 'dtok'] += 1
                 self._n_reads += n_reads
                 if dmaps is not None and n_reads:
                     self._device_maps(sample, *dmaps)
                     lap['maps'] = lap.get('maps', 0.0) + \
                         time.perf_counter() - t3
                 # (from here on the blocks of this file are scanned and
-                # emitted with one wait, until one is refused)
-                self._spec = not os.environ.get('WOLTKA_NO_SPEC')
+                # emitted with one wait, until one is refused; not under
+                # `--outcov`: that wait is the plain flavour's)
+                self._spec = not cover and \
+                    not os.environ.get('WOLTKA_NO_SPEC')
                 return n_reads
         self._spec = False
         n = 0
+        # (`cover`: the block's ranges are in the pile already)
         for _, (subj, qoff), _, names, *_ in self._host_block(
-                buf, fill, first, final, hdr_in, names=dmaps is not None):
+                buf, fill, first, final, hdr_in, names=dmaps is not None,
+                cover=cover):
             self._sync_subjects(data)
             if dmaps is not None:
                 n += self.run_chunk(data, None, None, sample, None, None,
@@ -1356,7 +1424,7 @@ class DeviceTextRoute:
                 continue
             n += self.run_chunk(data, None, None, sample, None, None, None,
                                 None, None, False, packed=(subj, qoff),
-                                packed_is_set=not self._dtrimsub)
+                                packed_is_set=not (self._dtrimsub or cover))
         self.tok.set_header_state(hdr)
         return n
 

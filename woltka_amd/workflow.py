@@ -24,7 +24,7 @@ import click
 import numpy as np
 
 from .align import NATIVE_FORMATS, infer_align_format, plain_mapper
-from .classify import Engine, exact_to_numbers
+from .classify import Engine, cover_on_device, exact_to_numbers
 from .file import (FilesAhead, id2file_from_dir, id2file_from_map, openzip, path2stem,
                    read_ids, read_map_1st, read_map_uniq, readzip, readzip_bytes,
                    stem2rank, write_readmap)
@@ -258,8 +258,9 @@ def _workflow_with_context(
             if comm is None and not stratmap and \
                     not os.environ.get('WOLTKA_NO_DTOK'):
                 from .routes.device_text import start_text_ahead
+                # (`--outcov`: the "ex" parsers' cut, like the coord-match)
                 start_text_ahead(fp0, input_fmt, device,
-                                 extra=bool(coords_fp),
+                                 extra=bool(coords_fp or outcov_dir),
                                  ordered=bool(outmap_dir))
     start_coords_ahead(coords_fp, zippers)
     try:
@@ -475,6 +476,16 @@ def classify(
                         # read maps of plain assigners, one sample per file:
                         # the lines are formatted on the device next to the
                         # tokenised text (csrc/wk_readmap.hpp)
+                        # `--outcov` on plain classification: the ranges
+                        # are united on the device too (csrc/wk_cover.hpp)
+                        dcover = cover is not None and not ordinal and \
+                            cover_on_device(
+                                fmt_, exclude=bool(exclude), demux=bool(demux),
+                                strata=bool(stratmap),
+                                outmap=rank2dir is not None, part=part,
+                                n_jobs_ok=engine.words_eligible(
+                                    identity=not trimsub),
+                                n_subjects=len(engine.subjects))
                         dmaps = None
                         if rank2dir is not None and not (
                                 ordinal or cover is not None or demux or
@@ -487,7 +498,8 @@ def classify(
                             want_strings=want_strings, want_samples=native_demux,
                             cover=cover, fmt=fmt_, part=part, words=words,
                             words_dev=words_dev, dmaps=dmaps,
-                            keep_empty=bool(ordinal and rank2dir is not None))
+                            keep_empty=bool(ordinal and rank2dir is not None),
+                            dcover=dcover)
                         if ordinal and rank2dir is not None:
                             chunks = engine.regroup_hits(chunks, n)
                     else:
@@ -524,7 +536,9 @@ def classify(
                             reads = qryque
                         # (optional) aligned ranges per (sample, subject)
                         # (parse_ranges, workflow.py:312)
-                        if cover is not None and native:
+                        if cover is not None and native and ranges is None:
+                            pass    # (united on the device: `_run_dcover`)
+                        elif cover is not None and native:
                             if demux:
                                 per_read = np.fromiter(
                                     (-1 if x is False else cover.sample(x)
@@ -565,6 +579,7 @@ def classify(
                 click.echo(f'  Number of sequences classified: {nqry}.')
 
         one_pass(rank2dir, cover)
+        engine.cover_flush(close=True)
         engine.finish(data, exact)
         # Cells whose exact value lies so close to a rounding boundary that
         # the reference's float summation might land on the other side are
