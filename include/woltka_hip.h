@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define WK_ABI_VERSION 1
+#define WK_ABI_VERSION 2
 
 /* error codes */
 #define WK_OK 0
@@ -79,7 +79,9 @@ extern "C" {
 #define WK_F_SUBOK 4u      /* --subok      (classify.py:75)      */
 #define WK_F_UNASSIGNED 8u /* --unassigned (workflow.py:1038-1039) */
 #define WK_F_SIZED 16u     /* --sizes: contributions go to the (feature, subject)
-                              log instead of the count table (classify.py:174-213) */
+                              log -- on packed records: the row pile of
+                              wk_sized_fetch -- instead of the count table
+                              (classify.py:174-213) */
 
 /* subj_flags of wk_chunk_stage / wk_classify_chunk */
 #define WK_SUBJ_IS_SET 1
@@ -271,6 +273,25 @@ int wk_words_append(wk_ctx* ctx, const uint32_t* words, int64_t n_records,
 int wk_words_wait(wk_ctx* ctx, int slot);
 int wk_words_flush(wk_ctx* ctx);
 int wk_words_pending(wk_ctx* ctx, int64_t* n_records, int64_t* n_reads);
+
+/* ---- size-normalised plain jobs on packed records (csrc/wk_sized.hpp) -------
+ * classify.counter_size (classify.py:174-213) for the job sets the weighted
+ * histogram takes, all of them WK_F_SIZED: wk_words_begin accepts such a set
+ * (next to unsized jobs it is refused), and wk_words_flush turns the sample's
+ * records into the rows the generic evaluator would have logged one by one --
+ * {feature, subject feature id, job << 16 | divisor, group} -- each once, with
+ * the number of times it occurs.  The rows of successive flushes pile up on the
+ * device until they are fetched.
+ *   wk_sized_pending  *n_rows = rows held; *n_flushes = flushes that added rows
+ *                     since the context was created.  (Records not flushed yet
+ *                     are not in either number.)
+ *   wk_sized_fetch    flushes, then copies the rows (rows[i][0..3], counts[i])
+ *                     and empties the pile.  *n = rows held; WK_E_CAPACITY when
+ *                     cap < *n: nothing is written or dropped, call again with
+ *                     room for *n.  Order is unspecified. */
+int wk_sized_pending(wk_ctx* ctx, int64_t* n_rows, int64_t* n_flushes);
+int wk_sized_fetch(wk_ctx* ctx, int32_t* rows, int64_t* counts, int64_t cap,
+                   int64_t* n);
 
 /* ---- SAM tokenizer on the device (plain flavour) --------------------------
  * align.parse_sam_file + plain_mapper (align.py:258-347, 47-115) on the GPU

@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get('WOLTKA_HIP_LIB') or os.path.join(
     _HERE, 'libwoltka_hip.so')
 
 # constants mirrored from include/woltka_hip.h
-ABI_VERSION = 1
+ABI_VERSION = 2
 OK, E_HIP, E_ARG, E_STATE, E_CAPACITY, E_RANGE, E_TABLE_FULL = (
     0, -1, -2, -3, -4, -5, -6)
 KEY_FEATURE_BITS, KEY_GROUP_BITS, KEY_K_BITS, KEY_JOB_BITS = 28, 21, 12, 3
@@ -45,6 +45,7 @@ SYMBOLS = (
     'wk_blob_join', 'wk_table_body', 'wk_table_rows', 'wk_host_alloc', 'wk_host_free', 'wk_host_register', 'wk_host_unregister',
     'wk_words_begin', 'wk_words_append',
     'wk_words_wait', 'wk_words_flush', 'wk_words_pending',
+    'wk_sized_pending', 'wk_sized_fetch',
     'wk_get_stats', 'wk_reset_stats', 'wk_timer_begin', 'wk_timer_end',
     'wk_timer_ms', 'wk_profile_kernels', 'wk_last_kernel_ms',
     'wk_tok_create', 'wk_tok_destroy', 'wk_tok_last_error',
@@ -159,6 +160,8 @@ def load_library():
         'wk_words_append': (C.c_int, [p, u32p, C.c_int64, C.c_int64, C.c_int]),
         'wk_words_wait': (C.c_int, [p, C.c_int]),
         'wk_words_flush': (C.c_int, [p]),
+        'wk_sized_pending': (C.c_int, [p, i64p, i64p]),
+        'wk_sized_fetch': (C.c_int, [p, i32p, i64p, C.c_int64, i64p]),
         'wk_words_pending': (C.c_int, [p, i64p, i64p]),
         'wk_get_stats': (C.c_int, [p, C.POINTER(Stats)]),
         'wk_reset_stats': (C.c_int, [p]),
@@ -594,6 +597,35 @@ class Context:
         self._check(self._lib.wk_words_pending(self._h, C.byref(a),
                                                C.byref(b)))
         return a.value, b.value
+
+    # -- size-normalised plain jobs on packed records (csrc/wk_sized.hpp) -----
+    def sized_pending(self):
+        """(rows the device holds, flushes that have added rows so far) of
+        the size-normalised job sets (classify.counter_size, classify.py:
+        174-213, on packed records)."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.wk_sized_pending(self._h, C.byref(a),
+                                               C.byref(b)))
+        return a.value, b.value
+
+    def sized_fetch(self):
+        """Flush, then (rows int32[n, 4] = (feature, subject feature, job <<
+        16 | divisor, group), counts int64[n]): every distinct contribution
+        of the samples flushed since the last fetch with the number of times
+        it occurs (what `log_fetch` lists one by one for the general route,
+        classify.py:174-213); empties the device's pile."""
+        n = C.c_int64(0)
+        rc = self._lib.wk_sized_fetch(self._h, None, None, 0, C.byref(n))
+        if rc == OK and n.value == 0:
+            return np.empty((0, 4), np.int32), np.empty(0, np.int64)
+        if rc not in (OK, E_CAPACITY):
+            self._check(rc)
+        rows = np.empty((n.value, 4), dtype=np.int32)
+        counts = np.empty(n.value, dtype=np.int64)
+        self._check(self._lib.wk_sized_fetch(
+            self._h, _ptr(rows, C.c_int32), _ptr(counts, C.c_int64), n.value,
+            C.byref(n)))
+        return rows[:n.value], counts[:n.value]
 
     # -- SAM tokenizer on the device -----------------------------------------
     def dtok_copy(self, buf, begin, stop):

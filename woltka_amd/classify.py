@@ -106,6 +106,7 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
         # and weighted by sizes[subject] on the host (classify.py:174-297)
         self.sizes = sizes
         self.sized = {}                 # (job, group key, feature, subj, div) -> n
+        self._sized_flushes = 0         # flushes of sized words counted in ROUTES
         if sizes:
             flags |= nat.F_SIZED
             self.ctx.log_reserve(1 << 22)

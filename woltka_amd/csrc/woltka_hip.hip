@@ -30,6 +30,7 @@
 #include "wk_readmap.hpp"
 #include "wk_tok_internal.h"
 #include "wk_weigh.hpp"
+#include "wk_sized.hpp"
 
 using namespace wk;
 
@@ -236,6 +237,10 @@ struct wk_ctx {
     int bins_ring = 4;  // measurement knob: load stages in flight of weigh_bins_kernel
     DevBuf w_slab, w_hi, w_invalid;
     size_t w_hi_clean = 0;        // leading entries of w_hi known to be zero
+    // size-normalised plain jobs (wk_sized.hpp): rows {feature, subject feature, job << 16 | divisor, group} and their
+    // counts, appended by every flush of such a job set until wk_sized_fetch takes them
+    DevBuf sz_rows, sz_counts, sz_scal;     // sz_scal: [0] non-zero bins of a flush, [1] rows appended by it
+    int64_t sz_n = 0, sz_flushes = 0;       // rows held; flushes that added some
     // read size per record of the staged chunk + reads the histogram does not
     // cover + totals: [0] derived at staging, [1] derived again with the
     // validity bits of the current subject rows (when some subject has one set)
@@ -1004,6 +1009,8 @@ int wk_create(int device, wk_ctx** out) {
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBinsMaxLds)) != hipSuccess ||
         (e = hipFuncSetAttribute(reinterpret_cast<const void*>(&weigh_streams_kernel<8>),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBinsMaxLds)) != hipSuccess ||
+        (e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sized_bins_kernel<4>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBinsMaxLds)) != hipSuccess ||
         (e = hipFuncSetAttribute(reinterpret_cast<const void*>(&weigh_merge_kernel),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024)) != hipSuccess ||
         (e = hipFuncSetAttribute(reinterpret_cast<const void*>(&classify_tiled_kernel),
@@ -1039,7 +1046,7 @@ void wk_destroy(wk_ctx* c) {
     DevBuf* bufs[] = {&c->nodes, &c->rank_code, &c->gene4, &c->g_grid, &c->g_first, &c->g_goff, &c->g_shift,
                       &c->tkeys, &c->tvals, &c->c_subj, &c->c_qoff, &c->c_group, &c->o_genome, &c->o_beg,
                       &c->o_end, &c->o_len, &c->o_hoff, &c->o_cnt, &c->o_ub, &c->o_first2, &c->o_poff, &c->o_pairs, &c->o_qoff,
-                      &c->o_tile_sum, &c->o_tile_off, &c->scalars, &c->stat_block, &c->log, &c->subj_feat, &c->subj_rows, &c->dense_slab, &c->plog, &c->plog_cnt, &c->left_mask, &c->left_list, &c->first_slab, &c->w_slab, &c->w_hi, &c->w_invalid, &c->c_rk[0], &c->c_rk[1], &c->rk_left[0], &c->rk_left[1], &c->rk_totals, &c->f_rank, &c->f_sparse, &c->f_dense, &c->w_renum, &c->f_log, &c->f_log_cnt, &c->f_partial, &c->f_part_used, &c->w_tmp, &c->assign_out, &c->fetch_k, &c->fetch_v};
+                      &c->o_tile_sum, &c->o_tile_off, &c->scalars, &c->stat_block, &c->log, &c->subj_feat, &c->subj_rows, &c->dense_slab, &c->plog, &c->plog_cnt, &c->left_mask, &c->left_list, &c->first_slab, &c->w_slab, &c->w_hi, &c->w_invalid, &c->sz_rows, &c->sz_counts, &c->sz_scal, &c->c_rk[0], &c->c_rk[1], &c->rk_left[0], &c->rk_left[1], &c->rk_totals, &c->f_rank, &c->f_sparse, &c->f_dense, &c->w_renum, &c->f_log, &c->f_log_cnt, &c->f_partial, &c->f_part_used, &c->w_tmp, &c->assign_out, &c->fetch_k, &c->fetch_v};
     for (DevBuf* b : bufs) b->release();
     for (wk_ctx::StreamTables& T : c->st)
         for (DevBuf* b : {&T.dsparse, &T.dparent, &T.dself, &T.rnode, &T.subj_node, &T.subj_rank}) b->release();
@@ -2175,9 +2182,14 @@ static int words_jobs_ok(wk_ctx* c, const wk_job* jobs, int32_t n_jobs, Classify
     }
     a = ClassifyArgs{};
     a.n_jobs = n_jobs;
+    // Size-normalised plain jobs (classify.counter_size, classify.py:174-213) are taken when the whole set is such jobs:
+    // their flush is the histogram over (subject, read size) of wk_sized.hpp.  Next to unsized jobs they are refused.
+    int n_sized = 0;
+    for (int j = 0; j < n_jobs; ++j) n_sized += (jobs[j].flags & WK_F_SIZED) ? 1 : 0;
+    if (n_sized && n_sized != n_jobs) return WK_OK;
     for (int j = 0; j < n_jobs; ++j) {
         const wk_job& jb = jobs[j];
-        if (jb.flags & (WK_F_UNIQ | WK_F_SIZED)) return WK_OK;
+        if (jb.flags & WK_F_UNIQ) return WK_OK;
         if (jb.mode == WK_MODE_RANK) {
             if ((jb.flags & WK_F_ABOVE) || jb.major > 0.0) return WK_OK;
             if (c->n_nodes <= 0) return fail(c, WK_E_STATE, "job %d needs a hierarchy (wk_set_tree)", j);
@@ -2205,6 +2217,142 @@ static bool same_jobs(const std::vector<wk_job>& have, const wk_job* jobs, int32
             have[j].major != jobs[j].major)
             return false;
     return true;
+}
+
+// The flush of a job set of size-normalised plain jobs (wk_sized.hpp): the table C[subject][read size] of the sample's
+// record streams, then one row per non-zero bin and job behind the rows of earlier flushes (wk_sized_fetch takes them).
+static int words_flush_sized(wk_ctx* c, const ClassifyArgs& a) {
+    const int32_t n_jobs = (int32_t)c->w_jobs.size();
+    const uint32_t cus = (uint32_t)c->prop.multiProcessorCount;
+    const int S = c->w_sliced ? c->w_streams : 1;
+    // sub-slices of every stream, and teams in proportion to its records: about one workgroup per CU in all
+    uint32_t n_q[kMaxStreams] = {}, teams[kMaxStreams] = {}, row_first[kMaxStreams] = {};
+    unsigned long long total = 0;
+    for (int k = 0; k < S; ++k) {
+        if (c->w_count[k] >= (1ull << 30)) return fail(c, WK_E_RANGE, "more than 2^30 records in one stream");
+        if (!c->w_count[k]) continue;
+        const int64_t lo = c->w_sliced ? (int64_t)k * kSliceBins : 0;
+        const int64_t held = std::max<int64_t>(0, c->w_sliced ? std::min<int64_t>(c->n_subjects - lo, kSliceBins) : c->n_subjects);
+        n_q[k] = (uint32_t)std::max<int64_t>(1, (held + kSizedSub - 1) / kSizedSub);
+        total += c->w_count[k];
+    }
+    uint32_t n_rows = 0;
+    for (int k = 0; k < S; ++k) {
+        if (!n_q[k]) continue;
+        const unsigned long long share = (unsigned long long)cus * c->w_count[k] / std::max<unsigned long long>(total, 1);  // workgroups this stream may have
+        const unsigned long long tiles = (c->w_count[k] + kSizedTile - 1) / kSizedTile;
+        uint32_t t = (uint32_t)std::max<unsigned long long>(1, std::min(share / n_q[k], tiles));
+        if (t >= 8u) t &= ~7u;  // (whole octets: a team on one XCD)
+        teams[k] = t;
+        row_first[k] = n_rows;
+        n_rows += n_q[k] * t;
+    }
+    HIP_TRY(c, c->w_slab.reserve((size_t)std::max(n_rows, 1u) * kSliceBins * 4));
+    HIP_TRY(c, c->sz_scal.reserve(16));
+    HIP_TRY(c, hipMemsetAsync(c->sz_scal.p, 0, 16, c->stream));
+    KernelTimer* kt = ktimer_begin(c, "sized_bins");
+    for (int k = 0; k < S; ++k) {
+        if (!n_q[k]) continue;
+        SizedBinsArgs ba{};
+        ba.words = c->w_stream[k].as<uint32_t>();
+        ba.n_records = (uint32_t)c->w_count[k];
+        ba.n_subjects = (uint32_t)c->n_subjects;
+        ba.q_first = c->w_sliced ? (uint32_t)k * kSizedSizes : 0u;
+        ba.n_q = n_q[k];
+        ba.n_teams = teams[k];
+        ba.slab = c->w_slab.as<uint32_t>() + (size_t)row_first[k] * kSliceBins;
+        ba.err = scalar_err(c);
+        hipLaunchKernelGGL((sized_bins_kernel<4>), dim3(n_q[k] * teams[k]), dim3(kSizedThreads), (size_t)kSliceBins * 4, c->stream, ba);
+    }
+    ktimer_end(c, kt);
+    HIP_TRY(c, hipGetLastError());
+    SizedRowsArgs ra{};
+    ra.slab = c->w_slab.as<uint32_t>();
+    // (a subject table that grew past the streams' slices since they were opened holds no records behind them)
+    ra.n_subjects = (uint32_t)(c->w_sliced ? std::min<int64_t>(c->n_subjects, (int64_t)S * kSliceBins) : c->n_subjects);
+    ra.sliced = c->w_sliced ? 1u : 0u;
+    for (int k = 0; k < S; ++k) {
+        ra.teams[k] = teams[k];
+        ra.row_first[k] = row_first[k];
+    }
+    ra.rows = a.rows;
+    ra.row_w = a.row_w;
+    ra.n_jobs = n_jobs;
+    for (int j = 0; j < n_jobs; ++j) {
+        ra.mode[j] = a.jobs[j].mode;
+        ra.col[j] = a.jobs[j].col;
+    }
+    ra.group = c->w_group;
+    ra.n_bins = c->sz_scal.as<unsigned long long>();
+    ra.cursor = c->sz_scal.as<unsigned long long>() + 1;
+    ra.err = scalar_err(c);
+    const dim3 rgrid((kSliceBins + kSizedRowsThreads - 1) / kSizedRowsThreads, std::max(1u, (ra.n_subjects + kSizedSub - 1) / kSizedSub));
+    kt = ktimer_begin(c, "sized_rows");
+    hipLaunchKernelGGL((sized_rows_kernel<false>), rgrid, dim3(kSizedRowsThreads), 0, c->stream, ra);
+    HIP_TRY(c, hipGetLastError());
+    unsigned long long n_bins = 0;
+    HIP_TRY(c, hipMemcpyAsync(&n_bins, c->sz_scal.p, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const int64_t more = (int64_t)n_bins * n_jobs;
+    if (more > 0) {
+        const size_t need = (size_t)(c->sz_n + more);
+        if (need * 16 > c->sz_rows.cap) {  // grow: new buffers (twice the need) take over the rows held
+            DevBuf rows, counts;
+            HIP_TRY(c, rows.reserve(need * 2 * 16));
+            hipError_t e = counts.reserve(need * 2 * 8);
+            if (e != hipSuccess) {
+                rows.release();
+                HIP_TRY(c, e);
+            }
+            if (c->sz_n > 0) {
+                (void)hipMemcpyAsync(rows.p, c->sz_rows.p, (size_t)c->sz_n * 16, hipMemcpyDeviceToDevice, c->stream);
+                (void)hipMemcpyAsync(counts.p, c->sz_counts.p, (size_t)c->sz_n * 8, hipMemcpyDeviceToDevice, c->stream);
+            }
+            e = hipStreamSynchronize(c->stream);
+            c->sz_rows.release();
+            c->sz_counts.release();
+            c->sz_rows = rows;
+            c->sz_counts = counts;
+            HIP_TRY(c, e);
+        }
+        ra.out_rows = c->sz_rows.as<int4>();
+        ra.out_counts = c->sz_counts.as<long long>();
+        ra.base = (unsigned long long)c->sz_n;
+        ra.cap = (unsigned long long)need;
+        hipLaunchKernelGGL((sized_rows_kernel<true>), rgrid, dim3(kSizedRowsThreads), 0, c->stream, ra);
+        HIP_TRY(c, hipGetLastError());
+        c->sz_n += more;
+        c->sz_flushes += 1;
+    }
+    ktimer_end(c, kt);
+    c->stat_extra_reads += c->w_reads;
+    c->stat_extra_records += c->w_records;
+    if (c->words_keep) return WK_OK;
+    return words_reset(c);
+}
+
+int wk_sized_pending(wk_ctx* c, int64_t* n_rows, int64_t* n_flushes) {
+    if (!c) return WK_E_ARG;
+    if (n_rows) *n_rows = c->sz_n;
+    if (n_flushes) *n_flushes = c->sz_flushes;
+    return WK_OK;
+}
+
+int wk_sized_fetch(wk_ctx* c, int32_t* rows, int64_t* counts, int64_t cap, int64_t* n) {
+    if (!c || !n) return WK_E_ARG;
+    DeviceGuard guard(c->device);
+    int rc = c->words_keep ? WK_OK : wk_words_flush(c);  // records still accumulated (wk_words_append) become rows now
+    if (rc) return rc;
+    if ((rc = check_device_errors(c))) return rc;
+    *n = c->sz_n;
+    if (c->sz_n > cap || (c->sz_n && (!rows || !counts)))
+        return fail(c, WK_E_CAPACITY, "output capacity %lld < %lld rows", (long long)cap, (long long)c->sz_n);
+    if (c->sz_n == 0) return WK_OK;
+    HIP_TRY(c, hipMemcpyAsync(rows, c->sz_rows.p, (size_t)c->sz_n * 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(counts, c->sz_counts.p, (size_t)c->sz_n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->sz_n = 0;
+    return WK_OK;
 }
 
 int wk_words_flush(wk_ctx* c) {
@@ -2325,6 +2473,7 @@ int wk_words_flush(wk_ctx* c) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         c->w_counts_known = true;
     }
+    if (c->w_jobs[0].flags & WK_F_SIZED) return words_flush_sized(c, a);
     if ((size_t)c->n_subjects > c->w_hi_clean) {
         HIP_TRY(c, c->w_hi.reserve((size_t)c->n_subjects * 4 + ((size_t)c->n_subjects * 4) / 2));
         HIP_TRY(c, hipMemsetAsync(c->w_hi.p, 0, c->w_hi.cap, c->stream));

@@ -1384,6 +1384,8 @@ class DeviceTextRoute:
         t0 = time.perf_counter()
         self._sync_subjects(data)
         t1 = time.perf_counter()
+        if self.sizes:      # (rows of the samples flushed so far, once many)
+            self._collect_sized(force=False)
         began = self.ctx.words_begin(self.jobs, group)
         t2 = time.perf_counter()
         lap['subjects'] = lap.get('subjects', 0.0) + t1 - t0

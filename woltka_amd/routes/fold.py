@@ -9,6 +9,7 @@ from math import gcd
 import numpy as np
 
 from .. import _native as nat
+from ..hostio import ROUTES
 
 
 class Folding:
@@ -116,6 +117,24 @@ class Folding:
             key = (self._job_base + (meta >> 16), groups[g], f, s,
                    meta & 0xFFFF)
             acc[key] = acc.get(key, 0) + c
+
+    # rows the device may hold before they are folded in between two folds of
+    # the count table (16 + 8 bytes each)
+    SIZED_ROWS_MAX = 1 << 24
+
+    def _collect_sized(self, force=True):
+        """The rows the flushes of size-normalised words have piled up on the
+        device (csrc/wk_sized.hpp) -> `self.sized`, under the keys
+        `_collect_log` makes.  Called wherever the counts are collected (the
+        rows carry group ids), and by the words routes when the pile has
+        grown large (``force=False``)."""
+        if not force and self.ctx.sized_pending()[0] < self.SIZED_ROWS_MAX:
+            return
+        rows, counts = self.ctx.sized_fetch()
+        flushes = self.ctx.sized_pending()[1]
+        ROUTES['sized_flush'] += flushes - self._sized_flushes
+        self._sized_flushes = flushes
+        fold_sized_rows(self.sized, rows, counts, self.groups, self._job_base)
 
     def _finish_sized(self, data):
         """value = sum over contributions of sizes[subject] / divisor."""
@@ -247,6 +266,8 @@ class Folding:
                     (self.ranks[self._job_base + j], sample), {})
                 dst[key] = dst.get(key, 0) + Fraction(nn, kk)
         self.ctx.counts_clear()
+        if self.sizes:      # (the rows of flushed words name these groups)
+            self._collect_sized()
         if keep_groups:
             return
         self.groups = []
@@ -423,6 +444,40 @@ class Folding:
                         store.x[i] = num / den
                 out[k] = (cells, big)
         return out
+
+
+def fold_sized_rows(acc, rows, counts, groups, job_base=0):
+    """Add rows of size-normalised contributions -- int32[n, 4] = (feature,
+    subject, job << 16 | divisor, group id) with the number of times each
+    occurs -- to ``acc``: {(job, group key, feature, subject, divisor): n},
+    the keys `Folding._collect_log` makes (``groups``: group id -> key).  Equal
+    rows are added up in numpy first; Python sees every distinct row once."""
+    rows = np.asarray(rows, dtype=np.int32).reshape(-1, 4)
+    counts = np.asarray(counts, dtype=np.int64)
+    if not rows.shape[0]:
+        return acc
+    # a row as two 64-bit words: (group, feature) and (meta, subject)
+    r = rows.astype(np.int64)
+    hi = (r[:, 3] << 32) | r[:, 0]
+    lo = (r[:, 2] << 32) | r[:, 1]
+    order = np.lexsort((lo, hi))
+    hi, lo = hi[order], lo[order]
+    first = np.concatenate(([True], (hi[1:] != hi[:-1]) | (lo[1:] != lo[:-1])))
+    starts = np.flatnonzero(first)
+    tot = np.add.reduceat(counts[order], starts)
+    u = r[order[starts]]
+    meta = u[:, 2]
+    jobs = (job_base + (meta >> 16)).tolist()
+    divs = (meta & 0xFFFF).tolist()
+    keys = zip(jobs, map(groups.__getitem__, u[:, 3].tolist()),
+               u[:, 0].tolist(), u[:, 1].tolist(), divs)
+    if acc:
+        get = acc.get
+        for key, c in zip(keys, tot.tolist()):
+            acc[key] = get(key, 0) + c
+    else:
+        acc.update(zip(keys, tot.tolist()))
+    return acc
 
 
 def exact_to_numbers(data):

@@ -12,13 +12,18 @@ from ..hostio import MAX_GROUPS
 class WordsRoute:
     """(mixin of classify.Engine)"""
 
-    def words_eligible(self, identity=True):
+    def words_eligible(self, identity=True, sized=False):
         """Can chunks go to the device as packed words, accumulated per
         sample (``wk_words_*``)?  The plain assigners only — what
         ``wk_words_begin`` checks once more against the subject table.
         ``identity``: the words come from the host tokenizer, whose ids must
-        be the subject indices (the device text route translates)."""
-        if self.sizes or self._replay is not None or \
+        be the subject indices (the device text route translates).
+        ``sized``: the caller can take `--sizes` this way (`sized_on_device`:
+        plain classification of a whole file); then a set of plain
+        size-normalised jobs is eligible too — its flush makes the rows of
+        the contribution log (csrc/wk_sized.hpp, `_collect_sized`).  Sized
+        jobs that look at whole reads keep the general route."""
+        if (self.sizes and not sized) or self._replay is not None or \
                 len(self.jobs) > nat.MAX_JOBS or \
                 (identity and not self._tok_identity) or \
                 os.environ.get('WOLTKA_NO_WORDS'):
@@ -37,7 +42,7 @@ class WordsRoute:
         if all(map(whole_reads, self.jobs)):
             return self.use_tree
         for job in self.jobs:
-            if job.flags & (nat.F_UNIQ | nat.F_SIZED):
+            if job.flags & nat.F_UNIQ:
                 return False
             if job.mode == nat.MODE_RANK and (job.flags & nat.F_ABOVE or
                                               job.major > 0):
@@ -45,6 +50,16 @@ class WordsRoute:
             if job.mode not in (nat.MODE_NONE, nat.MODE_RANK):
                 return False
         return True
+
+    @staticmethod
+    def sized_on_device(plain, part=None):
+        """Does `--sizes` keep the words route for this file?  Plain
+        classification only (``plain``: no `--outmap`, `--outcov`, `--demux`,
+        `--stratify`, `--coords`) of a whole file (``part``: a byte range of
+        a file keeps today's route).  ``WOLTKA_NO_DSIZES=1`` keeps every
+        `--sizes` call on the general route."""
+        return bool(plain and part is None and
+                    not os.environ.get('WOLTKA_NO_DSIZES'))
 
     def device_maps_eligible(self):
         """Can the read maps be formatted on the device (wk_readmap.hpp)?  The
@@ -91,6 +106,8 @@ class WordsRoute:
                     and not self._table_fixed:
                 self.collect(data, keep_groups=True)
                 self._reserve(8 * len(self.subjects) * len(self.jobs))
+        if self.sizes:      # (rows of the samples flushed so far, once many)
+            self._collect_sized(force=False)
         if self.ctx.words_begin(self.jobs, group):
             self.ctx.words_append(words, n, slot)
             # the buffer of the chunk before this one has been copied by now
@@ -111,6 +128,8 @@ class WordsRoute:
         self.ctx.chunk_stage(subj, qoff, group=group, subj_is_set=True,
                              indexed=True)
         self._classify_staged(data, False)
+        if self.sizes:
+            self._collect_log()
         return n
 
     def _words_done(self):

@@ -464,15 +464,18 @@ def classify(
                         plain = not (ordinal or cover is not None or
                                      want_names or native_strata or demux or
                                      rank2dir is not None)
+                        # (`--sizes`: the flush of a sample's words makes the
+                        # rows of the contribution log, csrc/wk_sized.hpp)
+                        sized = engine.sized_on_device(plain, part)
                         words = plain and not trimsub and \
-                            engine.words_eligible()
+                            engine.words_eligible(sized=sized)
                         # (`--trim-sub`: the device text route translates the
                         # names it meets into subjects; the host tokenizer's
                         # words cannot)
                         # (`--exclude`: the names of the set get no subject
                         # index, so the tokenizer's ids are none either)
                         words_dev = plain and bool(trimsub or exclude) and \
-                            engine.words_eligible(identity=False)
+                            engine.words_eligible(identity=False, sized=sized)
                         # read maps of plain assigners, one sample per file:
                         # the lines are formatted on the device next to the
                         # tokenised text (csrc/wk_readmap.hpp)
