@@ -71,6 +71,7 @@ struct FusedArgs {
     uint32_t unknown_cap;
     DtokState* state;
     DtokState* host_state;               // pinned host memory: the block's scalars, written by the last workgroup
+    const unsigned long long* backup_prev;   // [kMaxStreams] the streams' cursors in front of this block (the begin kernel's, or the block before's backup_next)
     unsigned long long* backup_next;     // [kMaxStreams] the streams' cursors behind this block (= in front of the next)
     uint32_t* host_seq;                  // pinned host memory or null: `seq` is stored there (system scope, release) once host_state is written
     uint32_t seq;
@@ -80,11 +81,49 @@ struct FusedArgs {
     uint32_t ablate;            // (measurement, wk_tune "fz_ablate": phases left out -- results are wrong then)
 };
 
+// The block's reads (low half) and lines (high half) while the kernel runs: one word behind the DtokState, so that a
+// workgroup leaves both with one add.  (A block's text is shorter than 2^32 bytes: neither half carries.)  The caller
+// reserves sizeof(DtokState) + 64 bytes; whoever clears *state clears this word.
+static_assert(sizeof(DtokState) % 8 == 0, "the packed totals are aligned");
+__device__ __forceinline__ unsigned long long* fz_totals(DtokState* state) { return reinterpret_cast<unsigned long long*>(state + 1); }
+
 // the streams' cursors put aside and the block's scalars cleared, in front of the fused kernel on its stream
 __global__ void dtok_fused_begin_kernel(unsigned long long* __restrict__ backup, const unsigned long long* __restrict__ cursor, DtokState* state) {
     if (threadIdx.x < (uint32_t)kMaxStreams) backup[threadIdx.x] = cursor[threadIdx.x];
-    if (threadIdx.x == 0) *state = DtokState{0u, 0u, 0ull, 0ull, 0ull, 0u, 0u};
+    if (threadIdx.x == 0) {
+        *state = DtokState{0u, 0u, 0ull, 0ull, 0ull, 0u, 0u};
+        *fz_totals(state) = 0ull;
+    }
 }
+
+// Wave scans in registers (DPP: row shifts, then the two row broadcasts of gfx9) -- no trip through the LDS crossbar
+// and no wait for it.  All 64 lanes must be active.
+template <int kCtrl, int kRowMask>
+__device__ __forceinline__ uint32_t fz_dpp_add(uint32_t v) {
+    return v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, kCtrl, kRowMask, 0xF, false);
+}
+// inclusive sum over the lanes of a wave
+__device__ __forceinline__ uint32_t fz_wave_scan(uint32_t v) {
+    static_assert(kWave == 64, "four rows of sixteen lanes");
+    v = fz_dpp_add<0x111, 0xF>(v);  // row_shr:1
+    v = fz_dpp_add<0x112, 0xF>(v);  // row_shr:2
+    v = fz_dpp_add<0x114, 0xF>(v);  // row_shr:4
+    v = fz_dpp_add<0x118, 0xF>(v);  // row_shr:8
+    v = fz_dpp_add<0x142, 0xA>(v);  // row_bcast:15 -- rows 1 and 3 take the row before's sum
+    v = fz_dpp_add<0x143, 0xC>(v);  // row_bcast:31 -- rows 2 and 3 take the first half's sum
+    return v;
+}
+__device__ __forceinline__ uint32_t fz_last_lane(uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)v, kWave - 1); }
+__device__ __forceinline__ uint32_t fz_wave_sum(uint32_t v) { return fz_last_lane(fz_wave_scan(v)); }
+__device__ __forceinline__ unsigned long long fz_first_lane64(unsigned long long v) {
+    return ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) |
+           (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+}
+// The newlines of a wave's chunks, round by round, as fields of one word: one scan numbers all three rounds and its
+// last lane holds the wave's count.  (A round of 64 chunks holds at most 1024 newlines, the last round's chunks fewer.)
+constexpr uint32_t kFzNlBits = 11, kFzNlMask = (1u << kFzNlBits) - 1u;
+static_assert(kFzRounds == 3 && kWave * 16u <= kFzNlMask, "two fields of 11 bits");
+static_assert(kFzChunksPerWave > 2u * kWave && (kFzChunksPerWave - 2u * kWave) * 16u < (1u << (32u - 2u * kFzNlBits)), "and one of 10");
 
 // 16 aligned bytes of the text, read once: kept out of the way of what the L2 should hold (the dictionary)
 __device__ __forceinline__ uint4 fz_load_stream(const unsigned char* p) {
@@ -240,6 +279,8 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
     static_assert(kFzStreams <= 4 && kFzLines < 65536, "four 16-bit counts");
     __shared__ unsigned long long gbase[kFzStreams];
     __shared__ uint32_t wtot[kFzWaves];
+    __shared__ unsigned long long gbase_out[kMaxStreams];                    // (the last workgroup) the streams' advance over the block
+    __shared__ unsigned long long wg_totals;                                 // reads | lines << 32 of this workgroup (the exit)
     __shared__ uint32_t own[2];                                              // first owned line, first line of the next tile's runs
     __shared__ uint32_t wg_flags;
     uint32_t* const info = info_ + kFzPad;
@@ -250,24 +291,35 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
     if (tid == 0) newc_packed = 0ull;
     if (tid < kFzPad) info_[tid] = kFiStart;   // (a walk back stops here at the latest; it never gets here: a run starts at or behind the first owned line)
     if (tid == 0) wg_flags = 0u;
-    uint32_t my_flags = 0, my_rec = 0, my_reads = 0, my_lines = 0;
+    if (tid == 0) wg_totals = 0ull;
+    uint32_t my_flags = 0, my_reads = 0, my_lines = 0;
     const uint32_t text_end = a.n + (a.open_end ? 1u : 0u);  // (a text without a last newline: as if one followed)
 
-    // all of one slice's buffer to its stream (every thread calls this)
-    auto flush = [&](uint32_t k) {
+    // Every slice's buffer to its stream (every thread calls this): the slices' ranges are reserved side by side -- one
+    // round trip to the cursors, whatever the number of slices -- and records that find no room raise kDtokSpill in
+    // wg_flags, seen by the reserving lane.  (The histogram does not care about the records' order: a slice that is
+    // not full leaves with the one that is.)
+    auto flush_all = [&](bool last) {
         __syncthreads();
-        const uint32_t cnt = (a.ablate & 64u) ? 0u : rcnt[k];
-        if (tid == 0) gbase[k] = cnt ? atomicAdd(&a.streams.cursor[k], (unsigned long long)cnt) : 0ull;
-        __syncthreads();
-        const unsigned long long base = gbase[k];
-        for (uint32_t i = tid; i < cnt; i += kFzThreads) {
-            if (base + i < a.streams.cap)
-                a.streams.out[k][base + i] = rbuf[k][i];
-            else
-                my_flags |= kDtokSpill;
+        if (tid < n_streams) {
+            const uint32_t cnt = (a.ablate & 64u) ? 0u : rcnt[tid];
+            unsigned long long base = 0ull;
+            if (cnt) {
+                base = atomicAdd(&a.streams.cursor[tid], (unsigned long long)cnt);
+                if (base + cnt > a.streams.cap) atomicOr(&wg_flags, kDtokSpill);
+            }
+            gbase[tid] = base;
         }
         __syncthreads();
-        if (tid == 0) rcnt[k] = 0u;
+        for (uint32_t k = 0; k < n_streams; ++k) {
+            const uint32_t cnt = (a.ablate & 64u) ? 0u : rcnt[k];
+            const unsigned long long base = gbase[k];
+            for (uint32_t i = tid; i < cnt; i += kFzThreads)
+                if (base + i < a.streams.cap) a.streams.out[k][base + i] = rbuf[k][i];
+        }
+        if (last) return;
+        __syncthreads();
+        if (tid < n_streams) rcnt[tid] = 0u;
         __syncthreads();
     };
 
@@ -292,7 +344,7 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
             if (cw < kFzChunksPerWave && p < a.n && p < w1) v[r] = fz_load_stream(a.text + p);  // (may pass n: the text's pad)
         }
         uint32_t marks[kFzRounds];
-        uint32_t nl_mine = 0;
+        uint32_t nl_packed = 0;
 #pragma unroll
         for (uint32_t r = 0; r < kFzRounds; ++r) {
             const uint32_t cw = r * kWave + lane;
@@ -309,14 +361,14 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
                     if (a.open_end && a.n >= p && a.n < p + 16u) m |= 1u << (a.n - p);  // (n itself ends an open last line)
                     if (p + 16u > w1) m &= (1u << (w1 - p)) - 1u;
                     marks[r] = m;
-                    nl_mine += (uint32_t)__popc(m);
+                    nl_packed |= (uint32_t)__popc(m) << (kFzNlBits * r);
                 }
             }
         }
-        {
-            const uint32_t s = (uint32_t)wave_sum((unsigned long long)nl_mine);
-            if (lane == 0) wtot[wave] = s;
-        }
+        // (one scan in registers: the wave's count now, the lines' numbers behind the barrier)
+        const uint32_t nl_inc = fz_wave_scan(nl_packed);
+        const uint32_t nl_wave = fz_last_lane(nl_inc);
+        if (lane == 0) wtot[wave] = (nl_wave & kFzNlMask) + ((nl_wave >> kFzNlBits) & kFzNlMask) + (nl_wave >> (2u * kFzNlBits));
         __syncthreads();
         uint32_t before = 0, total_nl = 0;
 #pragma unroll
@@ -334,21 +386,14 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
 #pragma unroll
             for (uint32_t r = 0; r < kFzRounds; ++r) {
                 const uint32_t c = wave * kFzChunksPerWave + r * kWave + lane;
-                const uint32_t x = (uint32_t)__popc(marks[r]);
-                uint32_t inc = x;
-#pragma unroll
-                for (uint32_t d = 1; d < (uint32_t)kWave; d <<= 1) {
-                    const uint32_t up = __shfl_up(inc, d, kWave);
-                    if (lane >= d) inc += up;
-                }
-                uint32_t at = line + inc - x;
+                uint32_t at = line + ((nl_inc >> (kFzNlBits * r)) & kFzNlMask) - (uint32_t)__popc(marks[r]);
                 uint32_t m = marks[r];
                 while (m) {
                     const uint32_t b = (uint32_t)__ffs((int)m) - 1u;
                     ls[++at] = (uint16_t)(c * 16u + b + 1u);
                     m &= m - 1u;
                 }
-                line += __shfl(inc, kWave - 1, kWave);
+                line += (nl_wave >> (kFzNlBits * r)) & kFzNlMask;
             }
         }
         __syncthreads();
@@ -545,7 +590,6 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
                     word = s | ((pos & 15u) << kWordSubjBits) | ((size & 31u) << kWordSizeShift);
                     sl = s / kSliceBins;
                     if (sl >= n_streams) sl = n_streams - 1u;  // (a subject beyond the table: the histogram reports it)
-                    ++my_rec;
                     my_reads += pos == 0u ? 1u : 0u;
                 }
             }
@@ -561,15 +605,16 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
                 if (add) {  // (wave-uniform)
                     unsigned long long base = 0;
                     if (lane == 0) base = atomicAdd(&newc_packed, add);
-                    base = __shfl(base, 0, kWave);
+                    base = fz_first_lane64(base);
                     at = (uint32_t)(base >> (16u * sl)) & 0xFFFFu;
                     at += mine_before;
                 }
             }
             __syncthreads();
             const unsigned long long newc = newc_packed;
-            for (uint32_t s2 = 0; s2 < n_streams; ++s2)
-                if (rcnt[s2] + ((uint32_t)(newc >> (16u * s2)) & 0xFFFFu) > kFzCap) flush(s2);  // (uniform: every thread reads the same counters)
+            bool full = false;
+            for (uint32_t s2 = 0; s2 < n_streams; ++s2) full |= rcnt[s2] + ((uint32_t)(newc >> (16u * s2)) & 0xFFFFu) > kFzCap;
+            if (full) flush_all(false);  // (uniform: every thread reads the same counters)
             if (rec) rbuf[sl][rcnt[sl] + at] = word;
             __syncthreads();
             if (tid < n_streams) rcnt[tid] += (uint32_t)(newc >> (16u * tid)) & 0xFFFFu;
@@ -577,28 +622,19 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
             __syncthreads();
         }
     }
-    for (uint32_t s2 = 0; s2 < n_streams; ++s2) flush(s2);
-    // the block's totals and flags: one set of adds per workgroup
+    // ---- the exit: two rounds of returning atomics per workgroup, the cursors and `done` ----
+    // The workgroup's reads and lines as one word in LDS and its flags, behind flush_all's first barrier; the block's
+    // records are the cursors' advance, which the last workgroup reads anyway.
     if (my_flags) atomicOr(&wg_flags, my_flags);
-    const unsigned long long rec_w = wave_sum((unsigned long long)my_rec), reads_w = wave_sum((unsigned long long)my_reads),
-                             lines_w = wave_sum((unsigned long long)my_lines);
-    __shared__ unsigned long long w_rec[kFzWaves], w_reads[kFzWaves], w_lines[kFzWaves];
-    if (lane == 0) {
-        w_rec[wave] = rec_w;
-        w_reads[wave] = reads_w;
-        w_lines[wave] = lines_w;
+    {
+        const uint32_t reads_w = fz_wave_sum(my_reads), lines_w = fz_wave_sum(my_lines);
+        const unsigned long long t = ((unsigned long long)lines_w << 32) | reads_w;
+        if (lane == 0 && t) atomicAdd(&wg_totals, t);
     }
+    flush_all(true);
     __syncthreads();
     if (tid == 0) {
-        unsigned long long nrec = 0, nreads = 0, nlines = 0;
-        for (uint32_t w = 0; w < kFzWaves; ++w) {
-            nrec += w_rec[w];
-            nreads += w_reads[w];
-            nlines += w_lines[w];
-        }
-        if (nrec) atomicAdd(&a.state->n_out, nrec);
-        if (nreads) atomicAdd(&a.state->n_reads, nreads);
-        if (nlines) atomicAdd(&a.state->n_lines, nlines);
+        if (wg_totals) __hip_atomic_fetch_add(fz_totals(a.state), wg_totals, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (nothing comes back)
         if (wg_flags) atomicOr(&a.state->flags, wg_flags);
         // The last workgroup through does what two more launches used to: the block's scalars to pinned host memory
         // (the host reads them once the stream has been waited for), the streams' cursors put aside as the next
@@ -609,17 +645,24 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
     __syncthreads();
     if (own[0]) {
         __threadfence();
-        if (tid < (uint32_t)kMaxStreams)
-            a.backup_next[tid] = __hip_atomic_load(&a.streams.cursor[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // (the cursors behind the block, and how far they are from those in front of it: the block's records)
+        if (tid < (uint32_t)kMaxStreams) {
+            const unsigned long long cur = __hip_atomic_load(&a.streams.cursor[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            a.backup_next[tid] = cur;
+            gbase_out[tid] = tid < n_streams ? cur - a.backup_prev[tid] : 0ull;
+        }
+        __syncthreads();
         if (tid == 0) {
             DtokState st{};
             st.flags = __hip_atomic_load(&a.state->flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             st.n_unknown = __hip_atomic_load(&a.state->n_unknown, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            st.n_out = __hip_atomic_load(&a.state->n_out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            st.n_reads = __hip_atomic_load(&a.state->n_reads, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            st.n_lines = __hip_atomic_load(&a.state->n_lines, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const unsigned long long totals = __hip_atomic_load(fz_totals(a.state), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            for (uint32_t k = 0; k < (uint32_t)kMaxStreams; ++k) st.n_out += gbase_out[k];
+            st.n_reads = totals & 0xFFFFFFFFull;
+            st.n_lines = totals >> 32;
             *a.host_state = st;
             *a.state = DtokState{0u, 0u, 0ull, 0ull, 0ull, 0u, 0u};
+            *fz_totals(a.state) = 0ull;
             __threadfence_system();
             if (a.host_seq) __hip_atomic_store(a.host_seq, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }

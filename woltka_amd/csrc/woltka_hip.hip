@@ -3463,6 +3463,7 @@ static int dtok_scan_impl(wk_ctx* c, wk_tok* tok, const char* text, int64_t begi
             HIP_TRY(c, c->w_backup3.reserve(kMaxStreams * 8));
             DevBuf& before = fz_bk(c, c->fz_parity);
             DevBuf& after = fz_bk(c, (c->fz_parity + 1) % 3);
+            fa.backup_prev = before.as<unsigned long long>();   // (the block's records: the cursors' advance over it)
             fa.backup_next = after.as<unsigned long long>();
             fa.host_state = reinterpret_cast<DtokState*>(c->host_back);   // (slot 0 of the pinned scratch)
             c->w_backup_cur = before.p;
@@ -3736,6 +3737,7 @@ int wk_dtok_scan_emit_begin(wk_ctx* c, wk_tok* tok, const char* text, int64_t be
     if (!c->lag_ev[c->lag_next_ev]) HIP_TRY(c, hipEventCreateWithFlags(&c->lag_ev[c->lag_next_ev], hipEventDisableTiming));
     L.ev = c->lag_ev[c->lag_next_ev];
     c->lag_next_ev ^= 1;
+    fa.backup_prev = fz_bk(c, L.ring).as<unsigned long long>();   // (the block's records: the cursors' advance over it)
     fa.backup_next = fz_bk(c, (L.ring + 1) % 3).as<unsigned long long>();
     fa.host_state = reinterpret_cast<DtokState*>(c->host_back + (size_t)L.host_slot * wk_ctx::kBackBytes);
     static_assert(sizeof(DtokState) <= 128 && wk_ctx::kBackBytes >= 132, "the slot's second half holds the block's sequence number");
