@@ -3,7 +3,7 @@
 // wk_dtok.hpp does a block of text in six launches (count -> tile_scan -> lines ->
 // parse -> runs -> first_emit): the text is read three times and every kernel
 // hands per-line arrays to the next through HBM (5.8x the text in fabric traffic,
-// profiles/r05_e2e_lca_profile.json).  Here a workgroup keeps a tile of text in
+// profiles/r05_e2e_lca_profile.json).  Here a workgroup keeps a window of text in
 // LDS and does everything align.parse_sam_file + plain_mapper do to its lines
 // (woltka/align.py:258-347, 47-115) in that one residency: line starts, the
 // first three tabs, FLAG -> mate, RNAME -> dictionary, runs of equal QNAME, the
@@ -11,19 +11,36 @@
 // 23 | size << 27, wk_weigh.hpp).  Per-line arrays never leave LDS; the text is
 // read from HBM once.
 //
-// Tiles and ownership.  The text of a block is cut into tiles of at most kFzTile bytes
-// (so many that every workgroup gets the same number of them: FusedArgs::tile).  A
-// run of equal QNAMEs belongs to the tile its first line starts in; the workgroup
-// of a tile therefore looks kFzBack bytes back (the line before its first one:
-// does that one continue a run?) and kFzFwd bytes ahead (the rest of its last
-// run).  A run that does not end inside the window, a line that starts in the tile
-// and does not end inside the window, more than kFzLines lines in a
-// window, or a line before the tile that cannot be found in the window's back
-// part is nothing this kernel guesses about: the first three set kDtokSpill (the
-// block is done again by the six kernels, which have no such limits), the last
-// is looked up in global memory.
+// Spans and ownership.  The text of a block is cut into one contiguous span per
+// workgroup (FusedArgs::span bytes, the block in equal shares).  A run of equal
+// QNAMEs belongs to the span its first mapped line starts in.  A workgroup
+// walks its span window by window (at most kFzWin bytes in LDS at a time).  The
+// first window looks kFzBack bytes back (the line before the span's first one:
+// does that one continue a run?); a window owns the runs up to the last run
+// start it sees -- that run may go on behind the window -- and the next window
+// begins at that very line, which is known to start a run: nothing is looked at
+// twice but the lines of that one run.  The last window looks kFzFwd bytes
+// behind the span (the rest of its last run) and stops at the first run that
+// starts at or behind the span's end; where it sees none, a span of several
+// windows goes on from the start of its last run with wide windows: each
+// reads up to kFzWin bytes from where it begins, past the kFzFwd bytes behind
+// the span, until that run's end is seen.  A span of at most kFzTile bytes is
+// one window -- kFzBack in front, the span, kFzFwd behind -- and looks no
+// further.  A run that begins its window and does not end inside it -- a
+// stretch of unmapped lines longer than a window behind or inside it -- is
+// carried: the words of its mapped lines (at most kFzCarry) are put aside, the
+// next window begins behind this one's last whole line with those words in
+// front of its own lines' and compares its first mapped line's QNAME with the
+// run's in global memory; the run's records leave where it ends.  A run of
+// more mapped lines than that which does not end inside its window, a line
+// that does not end inside the window it starts, more than kFzLines lines in
+// a window, or a line before the span that cannot be found in the window's
+// back part is nothing this kernel guesses about: the first three set
+// kDtokSpill (the block is done again by the six kernels, which have no such
+// limits), the last is looked up in global memory, as is the mapped line
+// behind unmapped lines that fill a span's whole first window.
 //
-// Records.  Workgroups are persistent (a few per CU, tiles taken round-robin)
+// Records.  Workgroups are persistent (a few per CU, one span each)
 // and keep up to kFzCap records per slice of the subject table in LDS; a full
 // buffer leaves with ONE returning atomic on the stream's cursor and coalesced
 // stores.  (A reservation per tile and slice would be 12 k atomics on one cache
@@ -51,9 +68,10 @@ constexpr uint32_t kFzChunksPerWave = (kFzChunks + kFzWaves - 1) / kFzWaves;
 constexpr uint32_t kFzRounds = (kFzChunksPerWave + kWave - 1) / kWave;
 constexpr uint32_t kFzLines = 1024;   // lines of a window
 constexpr uint32_t kFzStreams = 4;    // slices of the subject table (more: the unfused kernels)
-constexpr uint32_t kFzCap = 1024;     // records kept per slice (>= kFzLines: a tile's records always fit an empty buffer)
-static_assert(kFzCap >= kFzLines, "a tile's records fit an empty buffer");
+constexpr uint32_t kFzCap = 1024;     // records kept per slice (>= kFzLines: a window's records always fit an empty buffer)
+static_assert(kFzCap >= kFzLines, "a window's records fit an empty buffer");
 static_assert(kFzWin + 32 < 65536, "window offsets fit 16 bits");
+constexpr uint32_t kFzCarry = 256;    // mapped lines of a run that goes on behind its window, kept for the windows behind it
 
 constexpr uint32_t kDtokSpill = 64;   // the fused kernel's limits (see above): the unfused kernels take the block
 
@@ -61,8 +79,7 @@ struct FusedArgs {
     const unsigned char* text;  // [n] + 64 readable bytes behind (zero)
     uint32_t n;
     uint32_t open_end;          // the text's last byte is no newline: a line ends at n
-    uint32_t n_tiles;
-    uint32_t tile;              // bytes per tile (a multiple of 16, <= kFzTile): the block in equal shares of the workgroups' rounds
+    uint32_t span;              // bytes per workgroup (a multiple of 16, >= 4096): the block in equal shares; the grid is ceil(n / span)
     const struct DictSlot8* dict8;
     const uint4* names16;       // by id
     uint32_t dict_mask;
@@ -231,8 +248,9 @@ __device__ __forceinline__ int32_t fz_probe_end(const FusedArgs& a, FzProbe p, c
 }
 
 // The mapped line before text position `at` (a line start) that no window holds: its QNAME compared with
-// the n bytes at `q`.  true = the line at `at` starts a run.  (Global memory, a byte at a time: a tile whose
-// kFzBack bytes in front hold no complete mapped line -- long or unmapped lines.)
+// the n bytes at `q`.  true = the line at `at` starts a run.  (Global memory, a byte at a time: a span whose
+// kFzBack bytes in front hold no complete mapped line -- long or unmapped lines --, or a window behind one that
+// held unmapped lines only.)
 __device__ bool fz_starts_run_slow(const unsigned char* __restrict__ text, uint32_t at, const unsigned char* q, uint32_t qn) {
     uint32_t pos = at;
     while (pos > 0u) {
@@ -248,7 +266,7 @@ __device__ bool fz_starts_run_slow(const unsigned char* __restrict__ text, uint3
                 if (text[s + k] != q[k]) return true;
             return false;
         }
-        pos = s;  // (unmapped, or no row at all -- its tile sends the block to the host): the line before
+        pos = s;  // (unmapped, or no row at all -- its span sends the block to the host): the line before
     }
     return true;
 }
@@ -272,24 +290,24 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
     __shared__ __attribute__((aligned(16))) unsigned char txt[kFzChunks * 16 + 32];
     __shared__ uint16_t ls[kFzLines + 2];                                    // line starts (window offsets); ls[k + 1] - 1 = the newline of line k
     __shared__ uint16_t f_qn[kFzLines], f_rb[kFzLines], f_rn[kFzLines];      // QNAME length, RNAME offset and length
-    __shared__ __attribute__((aligned(16))) uint32_t info_[kFzPad + kFzLines + kFzPad + 8];
+    __shared__ __attribute__((aligned(16))) uint32_t info_[kFzPad + kFzCarry + kFzLines + kFzPad + 8];
+    __shared__ uint32_t carry[kFzCarry];                                     // the words of a run's lines seen in windows before this one
     __shared__ uint32_t rbuf[kFzStreams][kFzCap];
     __shared__ uint32_t rcnt[kFzStreams];
-    __shared__ unsigned long long newc_packed;   // records of the tile at hand, per slice: 16 bits each
+    __shared__ unsigned long long newc_packed;   // records of the window at hand, per slice: 16 bits each
     static_assert(kFzStreams <= 4 && kFzLines < 65536, "four 16-bit counts");
     __shared__ unsigned long long gbase[kFzStreams];
     __shared__ uint32_t wtot[kFzWaves];
     __shared__ unsigned long long gbase_out[kMaxStreams];                    // (the last workgroup) the streams' advance over the block
     __shared__ unsigned long long wg_totals;                                 // reads | lines << 32 of this workgroup (the exit)
-    __shared__ uint32_t own[2];                                              // first owned line, first line of the next tile's runs
+    __shared__ uint32_t own[4];                                              // first run start in the span, first at or behind its end, last of the window; the lines put aside
     __shared__ uint32_t wg_flags;
-    uint32_t* const info = info_ + kFzPad;
+    uint32_t* const info = info_ + kFzPad + kFzCarry;  // (lines of the window from 0 up, the carried lines of its first run below 0)
 
     const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
     const uint32_t n_streams = a.streams.n_streams;
     if (tid < kFzStreams) rcnt[tid] = 0u;
     if (tid == 0) newc_packed = 0ull;
-    if (tid < kFzPad) info_[tid] = kFiStart;   // (a walk back stops here at the latest; it never gets here: a run starts at or behind the first owned line)
     if (tid == 0) wg_flags = 0u;
     if (tid == 0) wg_totals = 0ull;
     uint32_t my_flags = 0, my_reads = 0, my_lines = 0;
@@ -323,21 +341,45 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
         __syncthreads();
     };
 
-    for (uint32_t tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
-        const uint32_t t0 = tile * a.tile;
-        const uint32_t t1 = min(t0 + a.tile, a.n);
-        const uint32_t w0 = t0 >= kFzBack ? t0 - kFzBack : 0u;
-        const uint32_t w1 = min(t0 + a.tile + kFzFwd, text_end);  // text positions [w0, w1) are looked at
-        const bool to_end = w1 == text_end;                  // every line from here to the end of the text is whole
-        __syncthreads();  // (the tile before is through with the arrays)
-        if (tid < 2u) own[tid] = 0xFFFFFFFFu;
+    // The span [t0, t1) of this workgroup, window by window.  (Everything that steers the loop is the same in every
+    // thread: the arguments, and words of LDS read behind a barrier.)
+    const uint32_t t0 = blockIdx.x * a.span;   // (< n: the grid is ceil(n / span))
+    const uint32_t t1 = a.n - t0 > a.span ? t0 + a.span : a.n;
+    const uint32_t span_w1 = (uint32_t)min((unsigned long long)t1 + kFzFwd, (unsigned long long)text_end);
+    uint32_t wpos = t0 >= kFzBack ? t0 - kFzBack : 0u;  // the window's first byte of text
+    uint32_t mode = 0u;       // 0: the span's first window; 1: the line at wpos starts a run; 2: it is not known whether it does
+    uint32_t counted = t0;    // the newlines in front of this position are in my_lines (windows of a span overlap)
+    bool wide = false;        // the span's last run did not end kFzFwd bytes behind the span: whole windows from its start on
+    uint32_t nc = 0u;         // lines in `carry`: the mapped lines so far of a run that began in a window before and has not ended
+    uint32_t cq_pos = 0u, cq_len = 0u;  // ... and where its QNAME is in the text
+    const uint32_t max_trips = a.span / 16u + 2u;
+    for (uint32_t trip = 0;; ++trip) {
+        // (never: every window begins at least one whole line behind the one before, or hands a carried run's records
+        // over first -- wide windows too, which may follow one another; only a span's first wide look may begin where
+        // the window before did)
+        if (trip >= max_trips) {
+            my_flags |= kDtokSpill;
+            break;
+        }
+        const uint32_t w0 = wpos & ~15u;
+        const uint32_t lead = wpos - w0;  // bytes of the line before in the first chunk (the first window begins at a chunk)
+        // text positions [w0, w1) are looked at
+        const uint32_t w1 = (uint32_t)min((mode == 0u ? (unsigned long long)t0 + kFzTile + kFzFwd : (unsigned long long)w0 + kFzWin),
+                                           (unsigned long long)(wide ? text_end : span_w1));
+        const bool to_end = w1 == text_end;   // every line from here to the end of the text is whole
+        const bool last_win = wide || w1 == span_w1;  // the span's last window: kFzFwd bytes behind the span, or the end of the text
+        __syncthreads();  // (the window before is through with the arrays)
+        if (tid < 3u) own[tid] = tid < 2u ? 0xFFFFFFFFu : 0u;
+        // (a walk back stops in front of the carried lines at the latest; it never gets there: their first one starts the run)
+        if (tid < kFzPad) info[-(int32_t)nc - 1 - (int32_t)tid] = kFiStart;
+        for (uint32_t i = tid; i < nc; i += kFzThreads) info[(int32_t)i - (int32_t)nc] = carry[i];
 
         // ---- the window into LDS; newlines per 16-byte chunk ----
         // (a wave takes kFzChunksPerWave consecutive chunks: no barrier inside the scan below)
         uint4 v[kFzRounds];
 #pragma unroll
-        for (uint32_t r = 0; r < kFzRounds; ++r) {  // (all loads under way before the first is looked at.  Loading a tile ahead, the
-            // registers kept through the tile, bought nothing: three workgroups per CU take turns at the memory anyway)
+        for (uint32_t r = 0; r < kFzRounds; ++r) {  // (all loads under way before the first is looked at.  Loading a window ahead, the
+            // registers kept through the window, bought nothing: three workgroups per CU take turns at the memory anyway)
             const uint32_t cw = r * kWave + lane;
             const uint32_t p = w0 + (wave * kFzChunksPerWave + cw) * 16u;
             v[r] = make_uint4(0u, 0u, 0u, 0u);
@@ -357,9 +399,10 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
                     uint32_t m = fz_nibble(fz_marks32(v[r].x, 0x0A0A0A0Au)) | (fz_nibble(fz_marks32(v[r].y, 0x0A0A0A0Au)) << 4) |
                                  (fz_nibble(fz_marks32(v[r].z, 0x0A0A0A0Au)) << 8) | (fz_nibble(fz_marks32(v[r].w, 0x0A0A0A0Au)) << 12);
                     if (p + 16u > a.n) m &= p >= a.n ? 0u : (1u << (a.n - p)) - 1u;  // (nothing behind n is text)
-                    if (p >= t0 && p < t1) my_lines += (uint32_t)__popc(m);          // (the block's lines: counted where they end)
+                    if (p >= counted && p < t1) my_lines += (uint32_t)__popc(m);     // (the block's lines: counted in the span they end in, once)
                     if (a.open_end && a.n >= p && a.n < p + 16u) m |= 1u << (a.n - p);  // (n itself ends an open last line)
                     if (p + 16u > w1) m &= (1u << (w1 - p)) - 1u;
+                    if (p < wpos) m &= ~((1u << (wpos - p)) - 1u);                   // (the tail of the line before is no text of this window)
                     marks[r] = m;
                     nl_packed |= (uint32_t)__popc(m) << (kFzNlBits * r);
                 }
@@ -376,12 +419,13 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
             before += w < wave ? wtot[w] : 0u;
             total_nl += wtot[w];
         }
-        // lines of the window: line k = [ls[k], ls[k + 1] - 1), k < total_nl whole (line 0 only when the window starts the text)
+        // lines of the window: line k = [ls[k], ls[k + 1] - 1), k < total_nl whole (line 0 of a span's first window only
+        // when it starts the text: that window begins in the middle of a line, the others at one)
         const bool too_many = total_nl + 1u > kFzLines || (a.ablate & (32u | 512u));
         if (too_many) {
             if (!(a.ablate & 512u)) my_flags |= kDtokSpill;
         } else {
-            if (tid == 0) ls[0] = 0;
+            if (tid == 0) ls[0] = (uint16_t)lead;
             uint32_t line = before;  // newlines in front of this wave's chunks
 #pragma unroll
             for (uint32_t r = 0; r < kFzRounds; ++r) {
@@ -397,14 +441,15 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
             }
         }
         __syncthreads();
-        // A line that STARTS in this tile and does not end inside the window is a line nobody sees whole: its tile is
-        // the one that would own a run it starts, and the tiles behind it find no run start in it.  (Lines of more
-        // than kFzFwd bytes -- SEQ / QUAL of a long read kept; text that comes through the column trim has none.)
-        if (!too_many && (total_nl > 0u || w0 == 0u)) {
-            const uint32_t trail = w0 + (uint32_t)ls[total_nl];   // the first byte behind the window's last newline
-            if (trail >= t0 && trail < t1) my_flags |= kDtokSpill;
-        }
-        const uint32_t first_line = w0 == 0u ? 0u : 1u;
+        // A line that STARTS in this span and does not end inside the span's last window is a line nobody sees whole:
+        // its span is the one that would own a run it starts, and the spans behind it find no run start in it.  (Lines
+        // of more than kFzFwd bytes -- SEQ / QUAL of a long read kept; text that comes through the column trim has
+        // none.)  In a window that is not the last, the next window begins in front of that line -- or does not get
+        // ahead, below.
+        // the first byte behind the window's last newline
+        const uint32_t trail = too_many ? wpos : w0 + (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ls[total_nl]);
+        if (!too_many && last_win && trail >= t0 && trail < t1) my_flags |= kDtokSpill;
+        const uint32_t first_line = mode != 0u || w0 == 0u ? 0u : 1u;
         const uint32_t n_lines = too_many ? 0u : total_nl;  // whole lines: [first_line, n_lines)
         if (tid < kFzPad) info[n_lines + tid] = kFiStart;   // (a walk ahead stops behind the last whole line)
         if (tid == 0 && first_line) info[0] = 0u;
@@ -461,9 +506,9 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
 
         // ---- a mapped line at or behind t0: does it start a run (QNAME against the mapped line before it)?  Its subject?
         // (the dictionary slot is on its way while the QNAMEs are compared; the lines behind the last owned run are
-        // looked up for nothing -- a sixth of the window)
+        // looked up for nothing: the rest of one run, and once per span what the kFzFwd bytes behind it hold)
         for (uint32_t k = first_line + tid; k < n_lines; k += kFzThreads) {
-            if (!(info[k] & kFiMapped) || w0 + ls[k] < t0) continue;
+            if (!(info[k] & kFiMapped) || w0 + ls[k] < t0) continue;  // (only in a first window: the others begin behind t0)
             const unsigned char* name = txt + f_rb[k];
             const uint32_t rn = f_rn[k];
             FzProbe probe;
@@ -482,7 +527,9 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
                 start = true;
             else if (found)
                 start = f_qn[j] != f_qn[k] || !fz_same(txt + ls[k], txt + ls[j], f_qn[k]);
-            else if (w0 == 0u)
+            else if (nc)  // (the mapped line before is the carried run's last)
+                start = f_qn[k] != cq_len || !fz_same(txt + ls[k], a.text + cq_pos, cq_len);
+            else if (mode == 1u || wpos == 0u)  // (the line the window before stopped at, or the first of the text)
                 start = true;
             else
                 start = fz_starts_run_slow(a.text, w0 + ls[first_line], txt + ls[k], f_qn[k]);
@@ -502,28 +549,98 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
             }
             // (this thread's own word; the others look at its mapped bit only)
             info[k] |= (start ? kFiStart : 0u) | (excluded ? kFiExcl : 0u) | (sid < 0 ? kFiSubj : ((uint32_t)sid & kFiSubj));
-            if (start) atomicMin(&own[w0 + ls[k] < t1 ? 0 : 1], k);
+            if (start) {
+                atomicMin(&own[w0 + ls[k] < t1 ? 0 : 1], k);
+                atomicMax(&own[2], k);
+            }
         }
         __syncthreads();
-        // owned lines: from the first run that starts in the tile to the first run that starts behind it
-        uint32_t ka = own[0], kb = own[1];
-        if (ka == 0xFFFFFFFFu) {
-            ka = kb = 0u;  // no run starts in this tile
-        } else if (kb == 0xFFFFFFFFu) {
-            if (to_end) {
-                kb = n_lines;
-            } else {  // the tile's last run may go on behind the window
+        // Owned lines [ka, kb): from the first run that starts in the span (a first window), the window's first line or
+        // the carried lines (below 0) to the first run that starts at or behind the span's end, or -- where the window
+        // sees none -- to the last run start it sees: that run may go on behind the window, and the next window begins
+        // with it.  A run that begins its window and does not end in it (a stretch of unmapped lines behind it, say) is
+        // carried: its lines' words are put aside, the next window begins behind this one's last whole line and has
+        // them in front of its own.  `more`: there is a next window, and it begins at `next`.
+        const uint32_t o0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)own[0]), o1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)own[1]);
+        const uint32_t last = (uint32_t)__builtin_amdgcn_readfirstlane((int)own[2]);  // (o0 != ~0: the window's last run start in the span)
+        const uint32_t lpos = w0 + (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ls[o0 != 0xFFFFFFFFu ? last : 0u]);  // ... and where it is
+        const bool has_first = nc != 0u || o0 != 0xFFFFFFFFu;
+        const int32_t first_own = nc ? -(int32_t)nc : (int32_t)o0;
+        int32_t ka = 0, kb = 0;
+        uint32_t next = 0u, next_mode = 0u, nc_next = 0u;
+        bool more = false, again = false, put_aside = false;
+        if (too_many) {
+            if ((a.ablate & (32u | 512u)) && !last_win) {  // (measurement: the loads and the newlines of every window)
+                next = w1;
+                next_mode = 2u;
+                more = true;
+            }
+        } else if (o1 != 0xFFFFFFFFu) {  // the span ends here
+            kb = (int32_t)o1;
+            ka = has_first ? first_own : kb;
+        } else if (to_end) {
+            kb = (int32_t)n_lines;
+            ka = has_first ? first_own : kb;
+        } else if (last_win && a.span <= kFzTile) {
+            // the span's last run may go on behind the window: a span of one window looks kFzFwd bytes ahead and no further
+            if (o0 != 0xFFFFFFFFu) my_flags |= kDtokSpill;
+        } else if (o0 != 0xFFFFFFFFu && (nc != 0u || last != o0 || lpos > wpos)) {
+            // the runs in front of the last start are whole; on from that start (behind the span's end: whole windows)
+            kb = (int32_t)last;
+            ka = first_own;
+            next = lpos;
+            next_mode = 1u;
+            more = true;
+            again = last_win;
+        } else if (o0 != 0xFFFFFFFFu && last_win && !wide) {
+            // the span's last run begins this window and does not end kFzFwd bytes behind the span: once more, a whole window
+            next = wpos;
+            next_mode = 1u;
+            more = again = true;
+        } else if (o0 != 0xFFFFFFFFu || nc != 0u) {
+            // one run from the window's first line (or from windows before) to its end: put aside, on behind the last whole line
+            put_aside = true;
+        } else if (!last_win) {  // no run starts in this window (unmapped lines, lines of a run of the span before): on behind its last whole line
+            next = trail;
+            next_mode = 2u;
+            more = trail > wpos && trail < t1;  // (what starts at or behind t1 is the next span's)
+            if (trail <= wpos) my_flags |= kDtokSpill;  // a line that does not end inside the window it starts
+        }
+        if (put_aside) {  // (uniform)
+            if (tid == 0) {
+                uint32_t c = nc;
+                for (uint32_t k = first_line; k < n_lines; ++k) {
+                    const uint32_t w = info[k];
+                    if (w & kFiMapped) {
+                        if (c < kFzCarry) carry[c] = w & ~(kFiFirst | kFiDropped);
+                        ++c;
+                    }
+                }
+                own[3] = c;  // (a word of its own: the other waves may still be reading own[0..2] above)
+            }
+            __syncthreads();
+            nc_next = (uint32_t)__builtin_amdgcn_readfirstlane((int)own[3]);
+            if (nc_next > kFzCarry || trail <= wpos) {  // a run of more lines than are kept, or a line that does not end inside its window
                 my_flags |= kDtokSpill;
-                ka = kb = 0u;
+                nc_next = 0u;
+            } else {
+                if (nc == 0u) {
+                    cq_pos = wpos;
+                    cq_len = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)f_qn[0]);
+                }
+                next = trail;
+                next_mode = 2u;
+                more = true;
+                again = last_win;
             }
         }
         // ---- first line of its read (run, mate) that names its subject (the plain parsers keep sets, align.py:309) ----
         // (walks read eight lines' words at a time: one trip to the LDS per eight lines instead of two per line)
-        for (uint32_t k = ka + tid; k < kb; k += kFzThreads) {
+        for (int32_t k = ka + (int32_t)tid; k < kb; k += (int32_t)kFzThreads) {
             const uint32_t mk = info[k];
             if (!(mk & kFiMapped)) continue;
             if (mk & kFiExcl) {  // the line its run starts with learns that the run is dropped (read behind the barrier)
-                uint32_t j = k;
+                int32_t j = k;
                 while (!(info[j] & kFiStart)) --j;
                 atomicOr(&info[j], kFiDropped);
                 continue;
@@ -531,10 +648,10 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
             bool dup = false;
             if (!(mk & kFiStart) && !(a.ablate & 2u)) {
                 bool done = false;
-                for (uint32_t j = k; !done; j -= 8u) {
+                for (int32_t j = k; !done; j -= 8) {
                     uint32_t w[8];
 #pragma unroll
-                    for (uint32_t i = 0; i < 8; ++i) w[i] = info[(int32_t)j - 1 - (int32_t)i];
+                    for (uint32_t i = 0; i < 8; ++i) w[i] = info[j - 1 - (int32_t)i];
 #pragma unroll
                     for (uint32_t i = 0; i < 8; ++i) {
                         dup |= !done && ((w[i] ^ mk) & kFiKey) == 0u;
@@ -547,8 +664,8 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
         }
         __syncthreads();
         // ---- records: position and size inside the read ----
-        for (uint32_t k0 = ka; k0 < kb; k0 += kFzThreads) {  // (uniform trip count: barriers inside)
-            const uint32_t k = k0 + tid;
+        for (int32_t k0 = ka; k0 < kb; k0 += (int32_t)kFzThreads) {  // (uniform trip count: barriers inside)
+            const int32_t k = k0 + (int32_t)tid;
             bool rec = false;
             uint32_t word = 0, sl = 0, at = 0;
             if (k < kb && (info[k] & kFiFirst) && !(a.ablate & 4u)) {
@@ -558,10 +675,10 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
                 if (!(a.ablate & (2u | 128u))) {
                     if (!(mk & kFiStart)) {
                         bool done = false;
-                        for (uint32_t j = k; !done; j -= 8u) {
+                        for (int32_t j = k; !done; j -= 8) {
                             uint32_t w[8];
 #pragma unroll
-                            for (uint32_t i = 0; i < 8; ++i) w[i] = info[(int32_t)j - 1 - (int32_t)i];
+                            for (uint32_t i = 0; i < 8; ++i) w[i] = info[j - 1 - (int32_t)i];
 #pragma unroll
                             for (uint32_t i = 0; i < 8; ++i) {
                                 pos += (!done && (w[i] & kFiFirst) && ((w[i] ^ mk) & kFiRead) == 0u) ? 1u : 0u;
@@ -571,10 +688,10 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
                         }
                     }
                     bool done = false;
-                    for (uint32_t j = k + 1u; !done; j += 8u) {
+                    for (int32_t j = k + 1; !done; j += 8) {
                         uint32_t w[8];
 #pragma unroll
-                        for (uint32_t i = 0; i < 8; ++i) w[i] = info[j + i];
+                        for (uint32_t i = 0; i < 8; ++i) w[i] = info[j + (int32_t)i];
 #pragma unroll
                         for (uint32_t i = 0; i < 8; ++i) {
                             done |= (w[i] & kFiStart) != 0u;
@@ -621,6 +738,12 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
             if (tid == 0) newc_packed = 0ull;
             __syncthreads();
         }
+        if (!more) break;
+        wpos = next;
+        mode = next_mode;
+        wide = again;
+        nc = nc_next;
+        counted = w1;  // (a multiple of 16, or the end of the text: behind that no newline is counted)
     }
     // ---- the exit: two rounds of returning atomics per workgroup, the cursors and `done` ----
     // The workgroup's reads and lines as one word in LDS and its flags, behind flush_all's first barrier; the block's

@@ -3235,6 +3235,17 @@ static void fz_handed_back(wk_ctx* c) {
 
 static DevBuf& fz_bk(wk_ctx* c, int i) { return i == 0 ? c->w_backup : i == 1 ? c->w_backup2 : c->w_backup3; }
 
+// The one-kernel tokenizer's geometry for a block of n bytes: one contiguous span per persistent workgroup
+// ("dtok_fused_per_cu" of them per CU), the block in equal shares -- every workgroup walks the same number of bytes, and
+// the halos in front of and behind a span are looked at once per workgroup, not once per 16 KB.  (64 MB over 768
+// workgroups: spans of 85.3 KB, five windows each.)  Returns the grid; a short block gets fewer, 4 KB spans.
+static unsigned fused_spans(const wk_ctx* c, uint32_t n, uint32_t* span) {
+    const uint64_t wgs = (uint64_t)c->prop.multiProcessorCount * (uint64_t)c->fused_per_cu;
+    const uint64_t share = (((uint64_t)n + wgs - 1) / wgs + 15u) & ~(uint64_t)15u;
+    *span = (uint32_t)std::max<uint64_t>(share, 4096u);
+    return (unsigned)(((uint64_t)n + *span - 1) / *span);
+}
+
 static int dtok_emit_launch(wk_ctx* c, bool* ordered_out, unsigned long long* totals);
 static int dtok_emit_finish(wk_ctx* c, bool keep, bool ordered, DtokState st, unsigned long long totals, int64_t* n_reads,
                             int64_t* n_records);
@@ -3432,17 +3443,7 @@ static int dtok_scan_impl(wk_ctx* c, wk_tok* tok, const char* text, int64_t begi
             fa.text = c->dt_text;
             fa.n = n;
             fa.open_end = open_end ? 1u : 0u;
-            // (tiles of equal size, as many as make every workgroup's share the same number of rounds: 4096 tiles
-            // of 16 KB over 768 workgroups are 5.33 rounds paid as 6 -- 6 rounds of 14.2 KB tiles do the same work in
-            // 0.89 of the time)
-            const unsigned wgs = (unsigned)(c->prop.multiProcessorCount * c->fused_per_cu);
-            {
-                const uint32_t rounds = (uint32_t)(((uint64_t)n + (uint64_t)wgs * kFzTile - 1) / ((uint64_t)wgs * kFzTile));
-                uint32_t tile = (uint32_t)(((uint64_t)n + (uint64_t)wgs * rounds - 1) / ((uint64_t)wgs * rounds));
-                tile = (tile + 15u) & ~15u;
-                fa.tile = std::min<uint32_t>(kFzTile, std::max<uint32_t>(tile, 4096u));
-            }
-            fa.n_tiles = (n + fa.tile - 1) / fa.tile;
+            const unsigned grid = fused_spans(c, n, &fa.span);
             fa.dict8 = c->d_dict2.as<DictSlot8>();
             fa.names16 = c->d_names16.as<uint4>();
             fa.dict_mask = c->dt_dict_mask;
@@ -3472,7 +3473,6 @@ static int dtok_scan_impl(wk_ctx* c, wk_tok* tok, const char* text, int64_t begi
             if (!c->fz_chain || c->fz_no_chain)
                 hipLaunchKernelGGL(dtok_fused_begin_kernel, dim3(1), dim3(64), 0, c->stream, before.as<unsigned long long>(),
                                    (const unsigned long long*)fa.streams.cursor, fa.state);
-            const unsigned grid = std::min<unsigned>(fa.n_tiles, wgs);
             hipLaunchKernelGGL(dtok_fused_kernel, dim3(grid), dim3(kFzThreads), 0, c->stream, fa);
             ktimer_end(c, kf);
             HIP_TRY(c, hipGetLastError());
@@ -3705,17 +3705,10 @@ int wk_dtok_scan_emit_begin(wk_ctx* c, wk_tok* tok, const char* text, int64_t be
     HIP_TRY(c, c->d_state.reserve(sizeof(DtokState) + 64));
     if (c->d_unknown.cap < (size_t)(1 << 20) * 8) HIP_TRY(c, c->d_unknown.reserve((size_t)(1 << 20) * 8));
     for (int i = 0; i < 3; ++i) HIP_TRY(c, fz_bk(c, i).reserve(kMaxStreams * 8));
-    const unsigned wgs = (unsigned)(c->prop.multiProcessorCount * c->fused_per_cu);
     fa.text = res ? res->dev : c->d_textptr[k];
     fa.n = n;
     fa.open_end = open_end ? 1u : 0u;
-    {
-        const uint32_t rounds = (uint32_t)(((uint64_t)n + (uint64_t)wgs * kFzTile - 1) / ((uint64_t)wgs * kFzTile));
-        uint32_t tile = (uint32_t)(((uint64_t)n + (uint64_t)wgs * rounds - 1) / ((uint64_t)wgs * rounds));
-        tile = (tile + 15u) & ~15u;
-        fa.tile = std::min<uint32_t>(kFzTile, std::max<uint32_t>(tile, 4096u));
-    }
-    fa.n_tiles = (n + fa.tile - 1) / fa.tile;
+    const unsigned grid = fused_spans(c, n, &fa.span);
     fa.dict8 = c->d_dict2.as<DictSlot8>();
     fa.names16 = c->d_names16.as<uint4>();
     fa.dict_mask = c->dt_dict_mask;
@@ -3753,7 +3746,7 @@ int wk_dtok_scan_emit_begin(wk_ctx* c, wk_tok* tok, const char* text, int64_t be
     if (!c->fz_chain || c->fz_no_chain)
         hipLaunchKernelGGL(dtok_fused_begin_kernel, dim3(1), dim3(64), 0, c->stream, fz_bk(c, L.ring).as<unsigned long long>(),
                            (const unsigned long long*)fa.streams.cursor, fa.state);
-    hipLaunchKernelGGL(dtok_fused_kernel, dim3(std::min<unsigned>(fa.n_tiles, wgs)), dim3(kFzThreads), 0, c->stream, fa);
+    hipLaunchKernelGGL(dtok_fused_kernel, dim3(grid), dim3(kFzThreads), 0, c->stream, fa);
     ktimer_end(c, kf);
     HIP_TRY(c, hipGetLastError());
     if (!c->lag_poll) HIP_TRY(c, hipEventRecord(L.ev, c->stream));
