@@ -283,8 +283,28 @@ constexpr uint32_t kFiRead = kFiMapped | (3u << kFiMateShift);          // same 
 constexpr uint32_t kFiKey = kFiRead | kFiSubj;                          // ... and the same subject
 constexpr uint32_t kFzPad = 8;                   // words in front of / behind the lines' words (walks read eight at a time)
 
-// the four 0x80 marks of a word (bits 7, 15, 23, 31) as bits 0-3
-__device__ __forceinline__ uint32_t fz_nibble(uint32_t z) { return ((z >> 7) * 0x00204081u >> 21) & 15u; }
+// The 0x80 marks of two words (bits 7, 15, 23, 31 of each) as bits 0-7, the first word's in the low nibble: the second
+// word's marks go between the first one's (bits 4, 12, 20, 28), and one multiplication gathers all eight.  (Mark 8j [+4]
+// times 2^(21 - 7j') lands on bit 8j - 7j' + 21 [+4]: 32 products on 32 different bits, so nothing carries, and only
+// j = j' falls into bits 21-28.)
+__device__ __forceinline__ uint32_t fz_octet(uint32_t z_lo, uint32_t z_hi) { return (((z_lo >> 7) | (z_hi >> 3)) * 0x00204081u >> 21) & 255u; }
+
+// the newlines of a 16-byte chunk as bits 0-15
+__device__ __forceinline__ uint32_t fz_newlines16(uint4 v) {
+    return fz_octet(fz_marks32(v.x, 0x0A0A0A0Au), fz_marks32(v.y, 0x0A0A0A0Au)) | (fz_octet(fz_marks32(v.z, 0x0A0A0A0Au), fz_marks32(v.w, 0x0A0A0A0Au)) << 8);
+}
+
+// the tabs among the 32 bytes at p (LDS, any alignment) as the bits of one word
+__device__ __forceinline__ uint32_t fz_tabs32(const unsigned char* p) {
+    unsigned long long w[4];
+#pragma unroll
+    for (uint32_t i = 0; i < 4; ++i) w[i] = fz_load64(p + 8u * i);
+    uint32_t m = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < 4; ++i)
+        m |= fz_octet(fz_marks32((uint32_t)w[i], 0x09090909u), fz_marks32((uint32_t)(w[i] >> 32), 0x09090909u)) << (8u * i);
+    return m;
+}
 
 __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu(6, 6))) dtok_fused_kernel(FusedArgs a) {
     __shared__ __attribute__((aligned(16))) unsigned char txt[kFzChunks * 16 + 32];
@@ -387,17 +407,34 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
         }
         uint32_t marks[kFzRounds];
         uint32_t nl_packed = 0;
+        // (the limits below in scalar registers: what a wave's 64 chunks of a round lie inside is decided once per wave)
+        const uint32_t in_lo = max(wpos, counted), in_hi = min(min(w1, a.n), t1);
+        const uint32_t wave_c0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(wave * kFzChunksPerWave));
 #pragma unroll
         for (uint32_t r = 0; r < kFzRounds; ++r) {
             const uint32_t cw = r * kWave + lane;
             const uint32_t c = wave * kFzChunksPerWave + cw;
             const uint32_t p = w0 + c * 16u;
             marks[r] = 0u;
-            if (cw < kFzChunksPerWave && c < kFzChunks) {
+            // The interior: all 64 chunks are chunks of this wave and of the window, text of this window from their
+            // first byte to their last, and their newlines are this span's to count -- none of the corrections of the
+            // other branch applies.  (Almost every wave of almost every window in the rounds that are full; what
+            // touches the window's or the span's ends, the overlap with the window before, or the last round's 33
+            // chunks goes the other way.)
+            const uint32_t rc0 = wave_c0 + r * kWave, rp0 = w0 + rc0 * 16u;  // (the wave's first chunk of the round)
+            const bool interior = (r + 1u) * kWave <= kFzChunksPerWave && rc0 + kWave <= kFzChunks && rp0 >= in_lo &&
+                                  (unsigned long long)rp0 + kWave * 16u <= in_hi;
+            if (interior) {  // (wave-uniform, scalar compares)
+                *reinterpret_cast<uint4*>(txt + c * 16u) = v[r];
+                const uint32_t m = fz_newlines16(v[r]);
+                const uint32_t cnt = (uint32_t)__popc(m);
+                my_lines += cnt;
+                marks[r] = m;
+                nl_packed |= cnt << (kFzNlBits * r);
+            } else if (cw < kFzChunksPerWave && c < kFzChunks) {
                 *reinterpret_cast<uint4*>(txt + c * 16u) = v[r];
                 if (p < w1) {
-                    uint32_t m = fz_nibble(fz_marks32(v[r].x, 0x0A0A0A0Au)) | (fz_nibble(fz_marks32(v[r].y, 0x0A0A0A0Au)) << 4) |
-                                 (fz_nibble(fz_marks32(v[r].z, 0x0A0A0A0Au)) << 8) | (fz_nibble(fz_marks32(v[r].w, 0x0A0A0A0Au)) << 12);
+                    uint32_t m = fz_newlines16(v[r]);
                     if (p + 16u > a.n) m &= p >= a.n ? 0u : (1u << (a.n - p)) - 1u;  // (nothing behind n is text)
                     if (p >= counted && p < t1) my_lines += (uint32_t)__popc(m);     // (the block's lines: counted in the span they end in, once)
                     if (a.open_end && a.n >= p && a.n < p + 16u) m |= 1u << (a.n - p);  // (n itself ends an open last line)
@@ -457,18 +494,32 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
         // ---- a thread per line: three tabs, FLAG, RNAME ----
         for (uint32_t k = first_line + tid; k < n_lines; k += kFzThreads) {
             const uint32_t s = ls[k], e = (uint32_t)ls[k + 1] - 1u;
+            // The tabs of the line's first 32 bytes as one mask, the bits at or behind the line's end cleared (a short
+            // line's 32 bytes reach into the next line), and its three lowest bits taken: no loop, no indexed array.
+            // (The 32 bytes lie inside txt wherever the line starts: 32 bytes of pad behind the last chunk.)
             uint32_t tab[3] = {0, 0, 0}, nt = 0;
-            for (uint32_t p = s; p < e && nt < 3u && !(a.ablate & 256u); p += 32u) {  // (32 bytes under way at a time: the usual line needs no second round)
-                unsigned long long w[4];
-#pragma unroll
-                for (uint32_t i = 0; i < 4; ++i) w[i] = fz_load64(txt + p + 8u * i);
-#pragma unroll
-                for (uint32_t i = 0; i < 4; ++i) {
-                    unsigned long long z = fz_eq_bytes(w[i], '\t');
-                    while (z && nt < 3u) {
-                        const uint32_t q = p + 8u * i + (((uint32_t)__ffsll((long long)z) - 1u) >> 3);
-                        if (q < e) tab[nt++] = q;
-                        z &= z - 1ull;
+            if (!(a.ablate & 256u)) {
+                uint32_t m = fz_tabs32(txt + s);
+                if (e - s < 32u) m &= (1u << (e - s)) - 1u;
+                nt = min((uint32_t)__popc(m), 3u);
+                tab[0] = s + (uint32_t)__ffs((int)m) - 1u;
+                m &= m - 1u;
+                tab[1] = s + (uint32_t)__ffs((int)m) - 1u;
+                m &= m - 1u;
+                tab[2] = s + (uint32_t)__ffs((int)m) - 1u;  // (the first `nt` of the three are tabs; the others are not looked at)
+                // fewer than three and the line goes on: a QNAME or an RNAME of some length (rare on the texts measured)
+                for (uint32_t p = s + 32u; nt < 3u && p < e; p += 32u) {
+                    m = fz_tabs32(txt + p);
+                    if (e - p < 32u) m &= (1u << (e - p)) - 1u;
+                    for (; m && nt < 3u; m &= m - 1u) {
+                        const uint32_t q = p + (uint32_t)__ffs((int)m) - 1u;
+                        if (nt == 0u)
+                            tab[0] = q;
+                        else if (nt == 1u)
+                            tab[1] = q;
+                        else
+                            tab[2] = q;
+                        ++nt;
                     }
                 }
             }
