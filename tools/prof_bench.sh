@@ -2,6 +2,8 @@
 # Profile the bench command on the GPU box: rocprofv3 kernel trace + stats, then
 # FETCH_SIZE and WRITE_SIZE in separate PMC passes; writes
 #   gpurun_out/<tag>/kernel_stats.csv, pmc_summary.txt, traffic.json
+# A rocprofv3 step that does not end with status 0 (a fault, an abort, its time limit) ends the script with that
+# status: nothing more is started on the GPU behind it, and its log stays next to the results, in the directory of <tag>.
 # usage: tools/prof_bench.sh <tag> <workload> <scale> <kernel-name-substring>
 set -u
 R=${GRAFT_REPO_ROOT:-$PWD}
@@ -10,8 +12,9 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 CMD="python $R/bench.py --workload $WL --scale $SCALE --steps ${STEPS:-20} --warmup 3 --full --headline-only --passes ${PASSES:-2} ${EXTRA:-}"
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -- $CMD > "$OUT/kt.log" 2>&1
-echo "kernel-trace rc=$?"
+timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -- $CMD > "$OUT/kt.log" 2>&1
+rc=$?; echo "kernel-trace rc=$rc"
+[ $rc -eq 0 ] || { tail -5 "$OUT/kt.log"; exit $rc; }
 f=$(find "$OUT/kt" -name "*kernel_stats.csv" 2>/dev/null | head -1)
 [ -n "$f" ] && cp "$f" "$OUT/kernel_stats.csv" && cut -c1-150 "$OUT/kernel_stats.csv" | head -8
 i=0
@@ -24,8 +27,9 @@ INSTS="SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ
 [ "${PMC_SETS:-all}" = all ] && sets+=("SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE" "TCC_HIT_sum TCC_MISS_sum" "$INSTS")
 for set in "${sets[@]}"; do
   i=$((i+1))
-  timeout 900 rocprofv3 --pmc $set --output-format csv -d "$OUT/pmc$i" -- $CMD > "$OUT/pmc$i.log" 2>&1
-  echo "pmc$i rc=$?"
+  timeout -k 10 900 rocprofv3 --pmc $set --output-format csv -d "$OUT/pmc$i" -- $CMD > "$OUT/pmc$i.log" 2>&1
+  rc=$?; echo "pmc$i rc=$rc"
+  [ $rc -eq 0 ] || { tail -5 "$OUT/pmc$i.log"; exit $rc; }
   f=$(find "$OUT/pmc$i" -name "*counter_collection.csv" 2>/dev/null | head -1)
   [ -n "$f" ] && cp "$f" "$OUT/pmc$i.csv"
 done

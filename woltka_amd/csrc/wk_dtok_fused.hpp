@@ -54,6 +54,7 @@
 // kernels on such a block.
 #pragma once
 #include "wk_dtok.hpp"
+#include "wk_dtok_planes.hpp"
 
 namespace wk {
 
@@ -72,6 +73,7 @@ constexpr uint32_t kFzCap = 1024;     // records kept per slice (>= kFzLines: a 
 static_assert(kFzCap >= kFzLines, "a window's records fit an empty buffer");
 static_assert(kFzWin + 32 < 65536, "window offsets fit 16 bits");
 constexpr uint32_t kFzCarry = 256;    // mapped lines of a run that goes on behind its window, kept for the windows behind it
+static_assert(kFzCarry + kFzLines <= kFpMaxLines && kFzThreads % kWave == 0, "a window's owned lines fit the planes, a wave's lines one word");
 
 constexpr uint32_t kDtokSpill = 64;   // the fused kernel's limits (see above): the unfused kernels take the block
 
@@ -276,12 +278,12 @@ constexpr uint32_t kFiSubj = (1u << 23) - 1u;   // subject index (all ones: not 
 constexpr uint32_t kFiMateShift = 24;
 constexpr uint32_t kFiMapped = 1u << 26;
 constexpr uint32_t kFiStart = 1u << 27;          // starts a run of equal QNAMEs
-constexpr uint32_t kFiFirst = 1u << 28;          // first line of its read (run, mate) that names its subject
+// (bit 28 was "first line of its read (run, mate) that names its subject": that is a bit of the planes now)
 constexpr uint32_t kFiExcl = 1u << 29;           // names a subject of the exclusion set
 constexpr uint32_t kFiDropped = 1u << 30;        // (on the line that starts a run) a line of the run does: the run is dropped whole
 constexpr uint32_t kFiRead = kFiMapped | (3u << kFiMateShift);          // same read of a run: same mate (and mapped)
 constexpr uint32_t kFiKey = kFiRead | kFiSubj;                          // ... and the same subject
-constexpr uint32_t kFzPad = 8;                   // words in front of / behind the lines' words (walks read eight at a time)
+constexpr uint32_t kFzPad = 8;                   // words in front of the lines' words (the duplicate walk reads eight at a time; nothing walks ahead any more)
 
 // The 0x80 marks of two words (bits 7, 15, 23, 31 of each) as bits 0-7, the first word's in the low nibble: the second
 // word's marks go between the first one's (bits 4, 12, 20, 28), and one multiplication gathers all eight.  (Mark 8j [+4]
@@ -312,6 +314,7 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
     __shared__ uint16_t f_qn[kFzLines], f_rb[kFzLines], f_rn[kFzLines];      // QNAME length, RNAME offset and length
     __shared__ __attribute__((aligned(16))) uint32_t info_[kFzPad + kFzCarry + kFzLines + kFzPad + 8];
     __shared__ uint32_t carry[kFzCarry];                                     // the words of a run's lines seen in windows before this one
+    __shared__ unsigned long long planes[kFpPlanes][kFpWords];               // the owned lines as bits: run starts, first lines per mate (wk_dtok_planes.hpp)
     __shared__ uint32_t rbuf[kFzStreams][kFzCap];
     __shared__ uint32_t rcnt[kFzStreams];
     __shared__ unsigned long long newc_packed;   // records of the window at hand, per slice: 16 bits each
@@ -488,7 +491,6 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
         if (!too_many && last_win && trail >= t0 && trail < t1) my_flags |= kDtokSpill;
         const uint32_t first_line = mode != 0u || w0 == 0u ? 0u : 1u;
         const uint32_t n_lines = too_many ? 0u : total_nl;  // whole lines: [first_line, n_lines)
-        if (tid < kFzPad) info[n_lines + tid] = kFiStart;   // (a walk ahead stops behind the last whole line)
         if (tid == 0 && first_line) info[0] = 0u;
 
         // ---- a thread per line: three tabs, FLAG, RNAME ----
@@ -663,7 +665,7 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
                 for (uint32_t k = first_line; k < n_lines; ++k) {
                     const uint32_t w = info[k];
                     if (w & kFiMapped) {
-                        if (c < kFzCarry) carry[c] = w & ~(kFiFirst | kFiDropped);
+                        if (c < kFzCarry) carry[c] = w & ~kFiDropped;
                         ++c;
                     }
                 }
@@ -686,18 +688,20 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
             }
         }
         // ---- first line of its read (run, mate) that names its subject (the plain parsers keep sets, align.py:309) ----
-        // (walks read eight lines' words at a time: one trip to the LDS per eight lines instead of two per line)
-        for (int32_t k = ka + (int32_t)tid; k < kb; k += (int32_t)kFzThreads) {
-            const uint32_t mk = info[k];
-            if (!(mk & kFiMapped)) continue;
-            if (mk & kFiExcl) {  // the line its run starts with learns that the run is dropped (read behind the barrier)
+        // (walks read eight lines' words at a time: one trip to the LDS per eight lines instead of two per line.)  What
+        // the lanes find leaves as the planes' words: a wave's 64 lines are one word of each plane, a ballot each -- so
+        // every wave takes every trip with all its lanes, and a lane without a line of its own says no to all five.
+        for (int32_t k0 = ka; k0 < kb; k0 += (int32_t)kFzThreads) {  // (uniform trip count: ballots inside)
+            const int32_t k = k0 + (int32_t)tid;
+            const uint32_t mk = k < kb ? info[k] : 0u;
+            const bool mapped = (mk & kFiMapped) != 0u, excl = mapped && (mk & kFiExcl);
+            if (excl) {  // the line its run starts with learns that the run is dropped (read behind the barrier)
                 int32_t j = k;
                 while (!(info[j] & kFiStart)) --j;
                 atomicOr(&info[j], kFiDropped);
-                continue;
             }
             bool dup = false;
-            if (!(mk & kFiStart) && !(a.ablate & 2u)) {
+            if (mapped && !excl && !(mk & kFiStart) && !(a.ablate & 2u)) {
                 bool done = false;
                 for (int32_t j = k; !done; j -= 8) {
                     uint32_t w[8];
@@ -710,8 +714,18 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
                     }
                 }
             }
-            // (bit 28 of this thread's own word; the walks above look at the other bits of other lines' words)
-            if (!dup) atomicOr(&info[k], kFiFirst);  // (an atomic: a line of an excluded subject may be marking this word as its run's start)
+            // (a line of both mate bits has sent the block back already; it counts among its like, as it did in the walks)
+            const bool first = mapped && !excl && !dup;
+            const uint32_t mate = (mk >> kFiMateShift) & 3u;
+            const uint32_t wi = (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)(k0 - ka) / kWave + wave));  // (the planes' word of this wave's 64 lines)
+            const bool put = lane == 0 && wi < kFpWords;
+            const unsigned long long p_start = __ballot(mapped && (mk & kFiStart));
+            if (put) planes[kFpStart][wi] = p_start;
+#pragma unroll
+            for (uint32_t m = 0; m < 4; ++m) {
+                const unsigned long long p_first = __ballot(first && mate == m);
+                if (put) planes[kFpFirst + m][wi] = p_first;
+            }
         }
         __syncthreads();
         // ---- records: position and size inside the read ----
@@ -719,37 +733,19 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
             const int32_t k = k0 + (int32_t)tid;
             bool rec = false;
             uint32_t word = 0, sl = 0, at = 0;
-            if (k < kb && (info[k] & kFiFirst) && !(a.ablate & 4u)) {
-                const uint32_t mk = info[k];
+            const uint32_t li = (uint32_t)(k - ka);  // (bit li % 64 = lane of word li / 64 of the planes)
+            const uint32_t mk = k < kb ? info[k] : 0u;
+            const unsigned long long* const mine = planes[kFpFirst + ((mk >> kFiMateShift) & 3u)];
+            if (k < kb && ((mine[li / 64u] >> (li % 64u)) & 1ull) && !(a.ablate & 4u)) {
                 uint32_t pos = 0, size = 1;
                 bool dropped = (mk & kFiStart) && (mk & kFiDropped);
                 if (!(a.ablate & (2u | 128u))) {
-                    if (!(mk & kFiStart)) {
-                        bool done = false;
-                        for (int32_t j = k; !done; j -= 8) {
-                            uint32_t w[8];
-#pragma unroll
-                            for (uint32_t i = 0; i < 8; ++i) w[i] = info[j - 1 - (int32_t)i];
-#pragma unroll
-                            for (uint32_t i = 0; i < 8; ++i) {
-                                pos += (!done && (w[i] & kFiFirst) && ((w[i] ^ mk) & kFiRead) == 0u) ? 1u : 0u;
-                                dropped |= !done && (w[i] & kFiStart) && (w[i] & kFiDropped);
-                                done |= (w[i] & kFiStart) != 0u;
-                            }
-                        }
-                    }
-                    bool done = false;
-                    for (int32_t j = k + 1; !done; j += 8) {
-                        uint32_t w[8];
-#pragma unroll
-                        for (uint32_t i = 0; i < 8; ++i) w[i] = info[j + (int32_t)i];
-#pragma unroll
-                        for (uint32_t i = 0; i < 8; ++i) {
-                            done |= (w[i] & kFiStart) != 0u;
-                            size += (!done && (w[i] & kFiFirst) && ((w[i] ^ mk) & kFiRead) == 0u) ? 1u : 0u;
-                        }
-                    }
-                    size += pos;
+                    // (the head and the end of the run from the starts' plane, the first lines of this mate between them
+                    // counted; the run's first line knows whether the run is dropped)
+                    const FpRead r = fp_read(planes[kFpStart], mine, li, (uint32_t)(kb - ka));
+                    pos = r.pos;
+                    size = r.size;
+                    dropped = (info[ka + (int32_t)r.head] & kFiDropped) != 0u;
                 }
                 if (size > (uint32_t)WK_WEIGHT_MAX_K) my_flags |= kDtokBigRead;
                 const uint32_t s = mk & kFiSubj;
