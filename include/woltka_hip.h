@@ -206,6 +206,19 @@ int wk_counts_fetch(wk_ctx* ctx, uint64_t* keys, int64_t* counts, int64_t cap,
  * the log overflowed — reserve more and re-run the chunk. */
 int wk_log_reserve(wk_ctx* ctx, int64_t n_entries);
 int wk_log_fetch(wk_ctx* ctx, int32_t* out, int64_t cap, int64_t* n);
+/* wk_log_reduce is wk_log_fetch without the download (csrc/wk_logred.hpp): the
+ * entries logged so far are reduced on the device to one row per distinct
+ * entry — all 128 bits compared — with the number of times it occurs, and
+ * appended behind the rows of the pile that wk_sized_pending counts and
+ * wk_sized_fetch takes (below); the log is emptied.  *n_rows_in = entries the
+ * log held, *n_distinct = rows appended (their counts add up to *n_rows_in;
+ * order is unspecified).  An empty log launches nothing and touches nothing.
+ * WK_E_CAPACITY (with *n_rows_in = entries needed) means the log overflowed,
+ * exactly as for wk_log_fetch: the log is emptied, the pile is untouched —
+ * reserve more and re-run the chunk.  WK_E_RANGE for a log of 2^31 entries or
+ * more (row indices are 32 bits): nothing is touched, wk_log_fetch still takes
+ * it.  The number of flushes wk_sized_pending reports does not change. */
+int wk_log_reduce(wk_ctx* ctx, int64_t* n_rows_in, int64_t* n_distinct);
 
 /* ---- per-chunk work ---------------------------------------------------- */
 /* Stage one packed chunk of plain-mapper output in HBM (replaces the

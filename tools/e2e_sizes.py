@@ -24,7 +24,20 @@ kernels: time, and for `sized_bins_kernel` GB/s over 4 B per record times the
 number of workgroups that read a record (the sub-slices of its stream: the
 grid size / teams is not in a trace, so the tool takes `--reads-per-record`
 -- 16 for streams whose slices are full, the sub-slices of the whole table
-for the unsliced layout -- and `--runs`, the classify calls in the trace)."""
+for the unsliced layout -- and `--runs`, the classify calls in the trace).
+
+`--jobs free | genus-uniq | mixed` runs a job set that looks at whole reads
+instead: every chunk then goes through the general evaluator's contribution
+log, and the routes alternated are the log reduced on the device
+(csrc/wk_logred.hpp) against `WOLTKA_NO_DLOG=1`, the log downloaded and folded
+on the host:
+
+    python tools/e2e_sizes.py --jobs free --records 20000000 --reps 3 \
+        --json profiles/logred_e2e.json
+
+With `--trace`, `--log-rows N` (the rows the logs of the traced run held, the
+sum of `log_rows` the run printed) gives `log_reduce_kernel` its GB/s over the
+16 B per row the algorithm has to read."""
 import argparse
 import contextlib
 import hashlib
@@ -47,10 +60,15 @@ from woltka_amd.workflow import workflow  # noqa: E402
 
 INPUTS = {'config3': 100_000, 'wide': 1_000_000}
 HBM_PEAK = 8.0e12       # bytes/s, MI355X
-KERNELS = ('sized_bins_kernel', 'sized_rows_kernel')
+KERNELS = ('sized_bins_kernel', 'sized_rows_kernel', 'log_reduce_kernel',
+           'log_emit_kernel')
+# --jobs: keyword arguments of workflow for job sets that look at whole reads
+JOBS = {'free': dict(ranks='free'),
+        'genus-uniq': dict(ranks='genus', uniq=True),
+        'mixed': dict(ranks='free,genus,none')}
 
 
-def trace_summary(trace, out_csv, records, reads_per_record, runs):
+def trace_summary(trace, out_csv, records, reads_per_record, runs, log_rows=0):
     import csv
     acc = {}
     with open(trace, newline='') as fh:
@@ -68,7 +86,8 @@ def trace_summary(trace, out_csv, records, reads_per_record, runs):
     lines = ['kernel,dispatches,total_ms,bytes,GB_per_s,share_of_hbm_peak']
     for key, (n, ns) in sorted(acc.items()):
         nbytes = 4 * records * reads_per_record * runs \
-            if key == 'sized_bins_kernel' else 0
+            if key == 'sized_bins_kernel' else \
+            16 * log_rows if key == 'log_reduce_kernel' else 0
         rate = nbytes / (ns * 1e-9) if ns else 0.0
         lines.append(f'{key},{n},{ns / 1e6:.3f},{nbytes},{rate / 1e9:.1f},'
                      f'{rate / HBM_PEAK:.4f}')
@@ -113,25 +132,31 @@ def tables_digest(out):
     return h.hexdigest()
 
 
-def one_run(inputs, tmp, new):
+def one_run(inputs, tmp, new, jobs=None):
     sam_dir, nodes, sizes = inputs[:3]
+    switch, route = ('WOLTKA_NO_DLOG', 'log_reduce') if jobs else \
+        ('WOLTKA_NO_DSIZES', 'sized_flush')
     if new:
-        os.environ.pop('WOLTKA_NO_DSIZES', None)
+        os.environ.pop(switch, None)
     else:
-        os.environ['WOLTKA_NO_DSIZES'] = '1'
+        os.environ[switch] = '1'
+    kw = dict(JOBS[jobs]) if jobs else dict(ranks='phylum,genus,species')
     out = tempfile.mkdtemp(dir=tmp)
     ROUTES.clear()
     t0 = time.perf_counter()
     with contextlib.redirect_stdout(io.StringIO()):
         workflow(input_fp=sam_dir, input_fmt='sam', nodes_fps=[nodes],
-                 ranks='phylum,genus,species', sizes=sizes, scale='1M',
-                 digits=3, output_fmt=False,
-                 output_fp=os.path.join(out, 'tables'))
+                 sizes=sizes, scale='1M', digits=3, output_fmt=False,
+                 output_fp=os.path.join(out, 'tables'), **kw)
     dt = time.perf_counter() - t0
     routes = dict(ROUTES)
-    if new != bool(routes.get('sized_flush')):
+    if new != bool(routes.get(route)) or (jobs and routes.get('sized_flush')):
         raise SystemExit(f'the run took another route than asked: {routes}')
-    return dt, tables_digest(os.path.join(out, 'tables')), routes
+    tables = os.path.join(out, 'tables')
+    if os.path.isfile(tables):      # (one rank: one file)
+        with open(tables, 'rb') as fh:
+            return dt, hashlib.sha256(fh.read()).hexdigest(), routes
+    return dt, tables_digest(tables), routes
 
 
 def main():
@@ -141,6 +166,10 @@ def main():
     ap.add_argument('--input', choices=sorted(INPUTS) + ['both'],
                     default='both')
     ap.add_argument('--route', choices=['both', 'new', 'old'], default='both')
+    ap.add_argument('--jobs', choices=sorted(JOBS), default=None,
+                    help='a job set of the general route: alternate the '
+                    'device-side reduction of its log with WOLTKA_NO_DLOG=1')
+    ap.add_argument('--log-rows', type=int, default=0)
     ap.add_argument('--workdir', default=None)
     ap.add_argument('--json', default=None)
     ap.add_argument('--trace', default=None,
@@ -151,9 +180,10 @@ def main():
                     help='classify calls in the trace (warm-up + repetitions)')
     a = ap.parse_args()
     if a.trace:
-        trace_summary(a.trace, a.csv, a.records, a.reads_per_record, a.runs)
+        trace_summary(a.trace, a.csv, a.records, a.reads_per_record, a.runs,
+                      a.log_rows)
         return
-    out = {'records_asked': a.records, 'reps': a.reps, 'cpus': len(
+    out = {'records_asked': a.records, 'reps': a.reps, 'jobs': a.jobs, 'cpus': len(
         os.sched_getaffinity(0)), 'inputs': {}}
     with tempfile.TemporaryDirectory(dir=a.workdir) as tmp:
         for name in (sorted(INPUTS) if a.input == 'both' else [a.input]):
@@ -167,12 +197,12 @@ def main():
             routes = [True, False] if a.route == 'both' else \
                 [a.route == 'new']
             for new in routes:          # warm-up: page cache, first contexts
-                one_run(inputs, work, new)
+                one_run(inputs, work, new, a.jobs)
             times = {r: [] for r in routes}
             digests, seen = {}, {}
             for _ in range(a.reps):
                 for new in routes:
-                    dt, dg, rt = one_run(inputs, work, new)
+                    dt, dg, rt = one_run(inputs, work, new, a.jobs)
                     times[new].append(dt)
                     digests[new], seen[new] = dg, rt
             res = {'subjects': INPUTS[name], 'records': records,

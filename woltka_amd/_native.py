@@ -37,7 +37,7 @@ SYMBOLS = (
     'wk_build_rank_table', 'wk_get_rank_table', 'wk_set_genes',
     'wk_set_subjects',
     'wk_counts_reserve', 'wk_counts_clear', 'wk_counts_fetch',
-    'wk_log_reserve', 'wk_log_fetch',
+    'wk_log_reserve', 'wk_log_fetch', 'wk_log_reduce',
     'wk_chunk_stage', 'wk_classify_staged', 'wk_classify_chunk',
     'wk_ordinal_stage', 'wk_ordinal_match', 'wk_ordinal_count',
     'wk_set_uniform_group', 'wk_chunk_download', 'wk_ordinal_hit_offsets',
@@ -133,6 +133,7 @@ def load_library():
         'wk_counts_fetch': (C.c_int, [p, u64p, i64p, C.c_int64, i64p]),
         'wk_log_reserve': (C.c_int, [p, C.c_int64]),
         'wk_log_fetch': (C.c_int, [p, i32p, C.c_int64, i64p]),
+        'wk_log_reduce': (C.c_int, [p, i64p, i64p]),
         'wk_chunk_stage': (C.c_int, [p, i32p, i32p, C.c_int64, i32p,
                                      C.c_int]),
         'wk_classify_staged': (C.c_int, [p, C.POINTER(Job), C.c_int32, i32p]),
@@ -479,6 +480,16 @@ class Context:
         self._check(self._lib.wk_log_fetch(self._h, _ptr(out, C.c_int32),
                                            self._log_cap, C.byref(n)))
         return out[:n.value]
+
+    def log_reduce(self):
+        """The contribution log reduced on the device (csrc/wk_logred.hpp):
+        its distinct entries go, each once with the number of times it occurs,
+        behind the rows `sized_fetch` takes; empties the log.  Returns
+        (entries the log held, distinct rows appended); `OverflowError` when
+        the log overflowed, as for `log_fetch`."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.wk_log_reduce(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     # -- classify ---------------------------------------------------------
     @staticmethod

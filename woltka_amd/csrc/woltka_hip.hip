@@ -31,6 +31,7 @@
 #include "wk_tok_internal.h"
 #include "wk_weigh.hpp"
 #include "wk_sized.hpp"
+#include "wk_logred.hpp"
 
 using namespace wk;
 
@@ -239,7 +240,8 @@ struct wk_ctx {
     size_t w_hi_clean = 0;        // leading entries of w_hi known to be zero
     // size-normalised plain jobs (wk_sized.hpp): rows {feature, subject feature, job << 16 | divisor, group} and their
     // counts, appended by every flush of such a job set until wk_sized_fetch takes them
-    DevBuf sz_rows, sz_counts, sz_scal;     // sz_scal: [0] non-zero bins of a flush, [1] rows appended by it
+    DevBuf sz_rows, sz_counts, sz_scal;     // sz_scal: [0] non-zero bins of a flush (distinct rows of a log), [1] rows appended by it
+    DevBuf lr_table;                        // wk_log_reduce: [slots] row indices, then [slots] counts
     int64_t sz_n = 0, sz_flushes = 0;       // rows held; flushes that added some
     // read size per record of the staged chunk + reads the histogram does not
     // cover + totals: [0] derived at staging, [1] derived again with the
@@ -1046,7 +1048,7 @@ void wk_destroy(wk_ctx* c) {
     DevBuf* bufs[] = {&c->nodes, &c->rank_code, &c->gene4, &c->g_grid, &c->g_first, &c->g_goff, &c->g_shift,
                       &c->tkeys, &c->tvals, &c->c_subj, &c->c_qoff, &c->c_group, &c->o_genome, &c->o_beg,
                       &c->o_end, &c->o_len, &c->o_hoff, &c->o_cnt, &c->o_ub, &c->o_first2, &c->o_poff, &c->o_pairs, &c->o_qoff,
-                      &c->o_tile_sum, &c->o_tile_off, &c->scalars, &c->stat_block, &c->log, &c->subj_feat, &c->subj_rows, &c->dense_slab, &c->plog, &c->plog_cnt, &c->left_mask, &c->left_list, &c->first_slab, &c->w_slab, &c->w_hi, &c->w_invalid, &c->sz_rows, &c->sz_counts, &c->sz_scal, &c->c_rk[0], &c->c_rk[1], &c->rk_left[0], &c->rk_left[1], &c->rk_totals, &c->f_rank, &c->f_sparse, &c->f_dense, &c->w_renum, &c->f_log, &c->f_log_cnt, &c->f_partial, &c->f_part_used, &c->w_tmp, &c->assign_out, &c->fetch_k, &c->fetch_v};
+                      &c->o_tile_sum, &c->o_tile_off, &c->scalars, &c->stat_block, &c->log, &c->subj_feat, &c->subj_rows, &c->dense_slab, &c->plog, &c->plog_cnt, &c->left_mask, &c->left_list, &c->first_slab, &c->w_slab, &c->w_hi, &c->w_invalid, &c->sz_rows, &c->sz_counts, &c->sz_scal, &c->lr_table, &c->c_rk[0], &c->c_rk[1], &c->rk_left[0], &c->rk_left[1], &c->rk_totals, &c->f_rank, &c->f_sparse, &c->f_dense, &c->w_renum, &c->f_log, &c->f_log_cnt, &c->f_partial, &c->f_part_used, &c->w_tmp, &c->assign_out, &c->fetch_k, &c->fetch_v};
     for (DevBuf* b : bufs) b->release();
     for (wk_ctx::StreamTables& T : c->st)
         for (DevBuf* b : {&T.dsparse, &T.dparent, &T.dself, &T.rnode, &T.subj_node, &T.subj_rank}) b->release();
@@ -2219,6 +2221,30 @@ static bool same_jobs(const std::vector<wk_job>& have, const wk_job* jobs, int32
     return true;
 }
 
+// Room for `need` rows in the pile of distinct rows (sz_rows / sz_counts): new buffers (twice the need) take over the
+// rows held.
+static int sized_pile_reserve(wk_ctx* c, size_t need) {
+    if (need * 16 <= c->sz_rows.cap && need * 8 <= c->sz_counts.cap) return WK_OK;
+    DevBuf rows, counts;
+    HIP_TRY(c, rows.reserve(need * 2 * 16));
+    hipError_t e = counts.reserve(need * 2 * 8);
+    if (e != hipSuccess) {
+        rows.release();
+        HIP_TRY(c, e);
+    }
+    if (c->sz_n > 0) {
+        (void)hipMemcpyAsync(rows.p, c->sz_rows.p, (size_t)c->sz_n * 16, hipMemcpyDeviceToDevice, c->stream);
+        (void)hipMemcpyAsync(counts.p, c->sz_counts.p, (size_t)c->sz_n * 8, hipMemcpyDeviceToDevice, c->stream);
+    }
+    e = hipStreamSynchronize(c->stream);
+    c->sz_rows.release();
+    c->sz_counts.release();
+    c->sz_rows = rows;
+    c->sz_counts = counts;
+    HIP_TRY(c, e);
+    return WK_OK;
+}
+
 // The flush of a job set of size-normalised plain jobs (wk_sized.hpp): the table C[subject][read size] of the sample's
 // record streams, then one row per non-zero bin and job behind the rows of earlier flushes (wk_sized_fetch takes them).
 static int words_flush_sized(wk_ctx* c, const ClassifyArgs& a) {
@@ -2296,25 +2322,8 @@ static int words_flush_sized(wk_ctx* c, const ClassifyArgs& a) {
     const int64_t more = (int64_t)n_bins * n_jobs;
     if (more > 0) {
         const size_t need = (size_t)(c->sz_n + more);
-        if (need * 16 > c->sz_rows.cap) {  // grow: new buffers (twice the need) take over the rows held
-            DevBuf rows, counts;
-            HIP_TRY(c, rows.reserve(need * 2 * 16));
-            hipError_t e = counts.reserve(need * 2 * 8);
-            if (e != hipSuccess) {
-                rows.release();
-                HIP_TRY(c, e);
-            }
-            if (c->sz_n > 0) {
-                (void)hipMemcpyAsync(rows.p, c->sz_rows.p, (size_t)c->sz_n * 16, hipMemcpyDeviceToDevice, c->stream);
-                (void)hipMemcpyAsync(counts.p, c->sz_counts.p, (size_t)c->sz_n * 8, hipMemcpyDeviceToDevice, c->stream);
-            }
-            e = hipStreamSynchronize(c->stream);
-            c->sz_rows.release();
-            c->sz_counts.release();
-            c->sz_rows = rows;
-            c->sz_counts = counts;
-            HIP_TRY(c, e);
-        }
+        const int grown = sized_pile_reserve(c, need);
+        if (grown) return grown;
         ra.out_rows = c->sz_rows.as<int4>();
         ra.out_counts = c->sz_counts.as<long long>();
         ra.base = (unsigned long long)c->sz_n;
@@ -2352,6 +2361,76 @@ int wk_sized_fetch(wk_ctx* c, int32_t* rows, int64_t* counts, int64_t cap, int64
     HIP_TRY(c, hipMemcpyAsync(counts, c->sz_counts.p, (size_t)c->sz_n * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->sz_n = 0;
+    return WK_OK;
+}
+
+// The contribution log of the chunk just classified as distinct rows with counts, behind the rows of the pile
+// (wk_logred.hpp); the log is emptied.
+int wk_log_reduce(wk_ctx* c, int64_t* n_rows_in, int64_t* n_distinct) {
+    if (!c || !n_rows_in || !n_distinct) return WK_E_ARG;
+    DeviceGuard guard(c->device);
+    *n_rows_in = *n_distinct = 0;
+    int rc = check_device_errors(c);
+    if (rc) return rc;
+    unsigned long long used = 0;
+    HIP_TRY(c, hipMemcpyAsync(&used, scalar_u64(c, 5), 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    *n_rows_in = (int64_t)used;
+    if (used == 0) return WK_OK;
+    if ((int64_t)used > c->log_cap) {
+        HIP_TRY(c, hipMemsetAsync(scalar_u64(c, 5), 0, 8, c->stream));
+        return fail(c, WK_E_CAPACITY, "contribution log overflowed: %llu entries needed, %lld reserved", used, (long long)c->log_cap);
+    }
+    // (the cursor stays: a call that fails below leaves the log to wk_log_fetch)
+    if (used >= (1ull << 31)) return fail(c, WK_E_RANGE, "a log of %llu rows cannot be reduced on the device (row indices are 32 bits); use wk_log_fetch", used);
+    KtScope kt_scope(c);
+    uint64_t slots = 1024;
+    while (slots < 2 * used) slots <<= 1;
+    HIP_TRY(c, c->lr_table.reserve((size_t)slots * 8));
+    HIP_TRY(c, c->sz_scal.reserve(16));
+    uint32_t* const tidx = c->lr_table.as<uint32_t>();
+    uint32_t* const tcnt = tidx + slots;
+    HIP_TRY(c, hipMemsetAsync(tidx, 0xFF, (size_t)slots * 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(tcnt, 0, (size_t)slots * 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->sz_scal.p, 0, 16, c->stream));
+    LogReduceArgs ra{};
+    ra.log = c->log.as<int4>();
+    ra.n_rows = (uint32_t)used;
+    ra.tidx = tidx;
+    ra.tcnt = tcnt;
+    ra.mask = (uint32_t)(slots - 1);
+    ra.n_distinct = c->sz_scal.as<unsigned long long>();
+    ra.err = scalar_err(c);
+    const uint64_t wgs = std::min<uint64_t>((used + kLogRedThreads - 1) / kLogRedThreads, (uint64_t)c->prop.multiProcessorCount * kLogRedWgPerCu);
+    KernelTimer* kt = ktimer_begin(c, "log_reduce");
+    hipLaunchKernelGGL(log_reduce_kernel, dim3((unsigned)wgs), dim3(kLogRedThreads), kLogRedFrontBytes, c->stream, ra);
+    ktimer_end(c, kt);
+    HIP_TRY(c, hipGetLastError());
+    unsigned long long distinct = 0;
+    HIP_TRY(c, hipMemcpyAsync(&distinct, c->sz_scal.p, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (distinct == 0 || distinct > used) return fail(c, WK_E_HIP, "log reduction counted %llu distinct rows of %llu", distinct, used);
+    const size_t need = (size_t)c->sz_n + (size_t)distinct;
+    if ((rc = sized_pile_reserve(c, need))) return rc;
+    LogEmitArgs ea{};
+    ea.log = ra.log;
+    ea.n_rows = ra.n_rows;
+    ea.tidx = tidx;
+    ea.tcnt = tcnt;
+    ea.slots = slots;
+    ea.out_rows = c->sz_rows.as<int4>();
+    ea.out_counts = c->sz_counts.as<long long>();
+    ea.cursor = c->sz_scal.as<unsigned long long>() + 1;
+    ea.base = (unsigned long long)c->sz_n;
+    ea.cap = (unsigned long long)need;
+    ea.err = scalar_err(c);
+    kt = ktimer_begin(c, "log_emit");
+    hipLaunchKernelGGL(log_emit_kernel, dim3((unsigned)((slots + kLogRedEmitThreads - 1) / kLogRedEmitThreads)), dim3(kLogRedEmitThreads), 0, c->stream, ea);
+    ktimer_end(c, kt);
+    HIP_TRY(c, hipGetLastError());
+    c->sz_n += (int64_t)distinct;
+    HIP_TRY(c, hipMemsetAsync(scalar_u64(c, 5), 0, 8, c->stream));
+    *n_distinct = (int64_t)distinct;
     return WK_OK;
 }
 

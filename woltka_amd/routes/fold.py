@@ -99,15 +99,35 @@ class Folding:
     def _collect_log(self):
         """Fold the contribution log of the chunk just classified.  If the log
         overflowed, enlarge it and run the staged chunk again (size-normalised
-        jobs write nothing but the log, so a re-run is harmless)."""
+        jobs write nothing but the log, so a re-run is harmless).
+
+        The log is reduced to its distinct rows on the device
+        (csrc/wk_logred.hpp) and those join the pile `_collect_sized` folds
+        -- the next `collect` takes them, while their group ids and
+        `_job_base` still hold.  ``WOLTKA_NO_DLOG=1``, or a log of 2^31 rows
+        and more (row indices are 32 bits), keeps the route that downloads
+        the log and folds it here."""
+        reduce = self.ctx._log_cap < 2 ** 31 and \
+            not os.environ.get('WOLTKA_NO_DLOG')
         while True:
             try:
-                rows = self.ctx.log_fetch()
+                if reduce:
+                    n_rows, n_distinct = self.ctx.log_reduce()
+                else:
+                    rows = self.ctx.log_fetch()
                 break
             except OverflowError:
                 self.ctx.log_reserve(self.ctx._log_cap * 4)
+                reduce = reduce and self.ctx._log_cap < 2 ** 31
                 self.ctx.classify_staged(
                     self.jobs[self._job_base:self._job_base + nat.MAX_JOBS])
+        if reduce:
+            if n_rows:
+                ROUTES['log_reduce'] += 1
+                ROUTES['log_rows'] += n_rows
+                ROUTES['log_distinct'] += n_distinct
+                self._collect_sized(force=False)
+            return
         if not rows.size:
             return
         uniq, cnt = np.unique(rows, axis=0, return_counts=True)
