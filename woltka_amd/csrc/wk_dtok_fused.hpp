@@ -55,6 +55,7 @@
 #pragma once
 #include "wk_dtok.hpp"
 #include "wk_dtok_planes.hpp"
+#include "wk_dtok_rounds.hpp"
 
 namespace wk {
 
@@ -64,9 +65,10 @@ constexpr uint32_t kFzTile = 16384;
 constexpr uint32_t kFzBack = 1024;
 constexpr uint32_t kFzFwd = 3072;
 constexpr uint32_t kFzWin = kFzTile + kFzBack + kFzFwd;
-constexpr uint32_t kFzChunks = kFzWin / 16 + 1;   // (+1: the byte behind a text without a last newline)
-constexpr uint32_t kFzChunksPerWave = (kFzChunks + kFzWaves - 1) / kFzWaves;
-constexpr uint32_t kFzRounds = (kFzChunksPerWave + kWave - 1) / kWave;
+constexpr uint32_t kFzChunks = kFzWin / 16 + 1;   // (+1: the chunk behind the window's text, wk_dtok_rounds.hpp)
+constexpr uint32_t kFzRounds = kFrMaxRounds;      // (the chunks are dealt to the waves in full rounds: wk_dtok_rounds.hpp)
+static_assert(kFrChunks * 16u == kFzWin && kFrTailChunk + 1u == kFzChunks && kFrWaves == kFzWaves && kFrWave == kWave,
+              "the dealing covers the window");
 constexpr uint32_t kFzLines = 1024;   // lines of a window
 constexpr uint32_t kFzStreams = 4;    // slices of the subject table (more: the unfused kernels)
 constexpr uint32_t kFzCap = 1024;     // records kept per slice (>= kFzLines: a window's records always fit an empty buffer)
@@ -82,6 +84,8 @@ struct FusedArgs {
     uint32_t n;
     uint32_t open_end;          // the text's last byte is no newline: a line ends at n
     uint32_t span;              // bytes per workgroup (a multiple of 16, >= 4096): the block in equal shares; the grid is ceil(n / span)
+                                // (a multiple of 16: a span's first window begins at a chunk then and is at most kFzWin bytes, as the
+                                // others are -- what wk_dtok_rounds.hpp's chunk behind the dealt ones rests on; the launch sites check it)
     const struct DictSlot8* dict8;
     const uint4* names16;       // by id
     uint32_t dict_mask;
@@ -138,11 +142,8 @@ __device__ __forceinline__ unsigned long long fz_first_lane64(unsigned long long
     return ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) |
            (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
 }
-// The newlines of a wave's chunks, round by round, as fields of one word: one scan numbers all three rounds and its
-// last lane holds the wave's count.  (A round of 64 chunks holds at most 1024 newlines, the last round's chunks fewer.)
-constexpr uint32_t kFzNlBits = 11, kFzNlMask = (1u << kFzNlBits) - 1u;
-static_assert(kFzRounds == 3 && kWave * 16u <= kFzNlMask, "two fields of 11 bits");
-static_assert(kFzChunksPerWave > 2u * kWave && (kFzChunksPerWave - 2u * kWave) * 16u < (1u << (32u - 2u * kFzNlBits)), "and one of 10");
+// (The newlines of a wave's chunks travel round by round as fields of one word: one scan numbers all three rounds and
+// its last lane holds the wave's count -- fr_pack / fr_unpack, wk_dtok_rounds.hpp.)
 
 // 16 aligned bytes of the text, read once: kept out of the way of what the L2 should hold (the dictionary)
 __device__ __forceinline__ uint4 fz_load_stream(const unsigned char* p) {
@@ -316,9 +317,8 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
     __shared__ uint32_t carry[kFzCarry];                                     // the words of a run's lines seen in windows before this one
     __shared__ unsigned long long planes[kFpPlanes][kFpWords];               // the owned lines as bits: run starts, first lines per mate (wk_dtok_planes.hpp)
     __shared__ uint32_t rbuf[kFzStreams][kFzCap];
-    __shared__ uint32_t rcnt[kFzStreams];
-    __shared__ unsigned long long newc_packed;   // records of the window at hand, per slice: 16 bits each
-    static_assert(kFzStreams <= 4 && kFzLines < 65536, "four 16-bit counts");
+    __shared__ unsigned long long fill_packed;   // records in the slices' buffers: 16 bits each (at most kFzCap and a trip's kFzThreads)
+    static_assert(kFzStreams <= 4 && kFzCap + kFzThreads < 65536, "four 16-bit counts");
     __shared__ unsigned long long gbase[kFzStreams];
     __shared__ uint32_t wtot[kFzWaves];
     __shared__ unsigned long long gbase_out[kMaxStreams];                    // (the last workgroup) the streams' advance over the block
@@ -328,9 +328,15 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
     uint32_t* const info = info_ + kFzPad + kFzCarry;  // (lines of the window from 0 up, the carried lines of its first run below 0)
 
     const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    const uint32_t wave_s = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave);  // (in a scalar register: what depends on it alone is wave-uniform)
     const uint32_t n_streams = a.streams.n_streams;
-    if (tid < kFzStreams) rcnt[tid] = 0u;
-    if (tid == 0) newc_packed = 0ull;
+    const uint32_t ablate = a.ablate;
+    const int32_t* const submap = a.submap;
+    // (the buffers' fill: the word in LDS is added to by the records loop alone; `fill` is what every thread read there
+    // behind that loop's barrier, the same in all of them)
+    unsigned long long fill = 0ull;
+    if (tid == 0) fill_packed = 0ull;
+    if (tid < 4u) reinterpret_cast<uint32_t*>(txt + kFrTailChunk * 16u)[tid] = 0u;  // (no wave's chunk and never text: wk_dtok_rounds.hpp)
     if (tid == 0) wg_flags = 0u;
     if (tid == 0) wg_totals = 0ull;
     uint32_t my_flags = 0, my_reads = 0, my_lines = 0;
@@ -339,11 +345,11 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
     // Every slice's buffer to its stream (every thread calls this): the slices' ranges are reserved side by side -- one
     // round trip to the cursors, whatever the number of slices -- and records that find no room raise kDtokSpill in
     // wg_flags, seen by the reserving lane.  (The histogram does not care about the records' order: a slice that is
-    // not full leaves with the one that is.)
-    auto flush_all = [&](bool last) {
+    // not full leaves with the one that is.)  `have`: the buffers' fill, packed as fill_packed is.
+    auto flush_all = [&](unsigned long long have, bool last) {
         __syncthreads();
         if (tid < n_streams) {
-            const uint32_t cnt = (a.ablate & 64u) ? 0u : rcnt[tid];
+            const uint32_t cnt = (ablate & 64u) ? 0u : (uint32_t)(have >> (16u * tid)) & 0xFFFFu;
             unsigned long long base = 0ull;
             if (cnt) {
                 base = atomicAdd(&a.streams.cursor[tid], (unsigned long long)cnt);
@@ -353,15 +359,13 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
         }
         __syncthreads();
         for (uint32_t k = 0; k < n_streams; ++k) {
-            const uint32_t cnt = (a.ablate & 64u) ? 0u : rcnt[k];
+            const uint32_t cnt = (ablate & 64u) ? 0u : (uint32_t)(have >> (16u * k)) & 0xFFFFu;
             const unsigned long long base = gbase[k];
             for (uint32_t i = tid; i < cnt; i += kFzThreads)
                 if (base + i < a.streams.cap) a.streams.out[k][base + i] = rbuf[k][i];
         }
         if (last) return;
-        __syncthreads();
-        if (tid < n_streams) rcnt[tid] = 0u;
-        __syncthreads();
+        __syncthreads();  // (the buffers are the caller's again)
     };
 
     // The span [t0, t1) of this workgroup, window by window.  (Everything that steers the loop is the same in every
@@ -398,60 +402,58 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
         for (uint32_t i = tid; i < nc; i += kFzThreads) info[(int32_t)i - (int32_t)nc] = carry[i];
 
         // ---- the window into LDS; newlines per 16-byte chunk ----
-        // (a wave takes kFzChunksPerWave consecutive chunks: no barrier inside the scan below)
+        // (a wave takes consecutive chunks, in full rounds -- wk_dtok_rounds.hpp: no barrier inside the scan below, and
+        // the waves of two rounds skip the third, uniformly)
+        const uint32_t wave_c0 = fr_first_chunk(wave_s), wave_rounds = fr_rounds(wave_s);
         uint4 v[kFzRounds];
 #pragma unroll
         for (uint32_t r = 0; r < kFzRounds; ++r) {  // (all loads under way before the first is looked at.  Loading a window ahead, the
             // registers kept through the window, bought nothing: three workgroups per CU take turns at the memory anyway)
-            const uint32_t cw = r * kWave + lane;
-            const uint32_t p = w0 + (wave * kFzChunksPerWave + cw) * 16u;
+            const uint32_t p = w0 + (wave_c0 + r * kWave + lane) * 16u;
             v[r] = make_uint4(0u, 0u, 0u, 0u);
-            if (cw < kFzChunksPerWave && p < a.n && p < w1) v[r] = fz_load_stream(a.text + p);  // (may pass n: the text's pad)
+            if (r < wave_rounds && p < a.n && p < w1) v[r] = fz_load_stream(a.text + p);  // (may pass n: the text's pad)
         }
         uint32_t marks[kFzRounds];
         uint32_t nl_packed = 0;
+        bool blank = false;  // (a chunk of more newlines than are counted: an empty line, see fr_chunk_marks)
         // (the limits below in scalar registers: what a wave's 64 chunks of a round lie inside is decided once per wave)
         const uint32_t in_lo = max(wpos, counted), in_hi = min(min(w1, a.n), t1);
-        const uint32_t wave_c0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(wave * kFzChunksPerWave));
 #pragma unroll
         for (uint32_t r = 0; r < kFzRounds; ++r) {
-            const uint32_t cw = r * kWave + lane;
-            const uint32_t c = wave * kFzChunksPerWave + cw;
+            const uint32_t c = wave_c0 + r * kWave + lane;
             const uint32_t p = w0 + c * 16u;
             marks[r] = 0u;
-            // The interior: all 64 chunks are chunks of this wave and of the window, text of this window from their
-            // first byte to their last, and their newlines are this span's to count -- none of the corrections of the
-            // other branch applies.  (Almost every wave of almost every window in the rounds that are full; what
-            // touches the window's or the span's ends, the overlap with the window before, or the last round's 33
-            // chunks goes the other way.)
-            const uint32_t rc0 = wave_c0 + r * kWave, rp0 = w0 + rc0 * 16u;  // (the wave's first chunk of the round)
-            const bool interior = (r + 1u) * kWave <= kFzChunksPerWave && rc0 + kWave <= kFzChunks && rp0 >= in_lo &&
-                                  (unsigned long long)rp0 + kWave * 16u <= in_hi;
+            if (r >= wave_rounds) continue;  // (wave-uniform)
+            // The interior: all 64 chunks are text of this window from their first byte to their last, and their
+            // newlines are this span's to count -- none of the corrections of the other branch applies.  (Almost
+            // every round of almost every window; what touches the window's or the span's ends or the overlap with
+            // the window before goes the other way.)
+            const uint32_t rp0 = w0 + (wave_c0 + r * kWave) * 16u;  // (the wave's first chunk of the round)
+            const bool interior = rp0 >= in_lo && (unsigned long long)rp0 + kWave * 16u <= in_hi;
+            *reinterpret_cast<uint4*>(txt + c * 16u) = v[r];
             if (interior) {  // (wave-uniform, scalar compares)
-                *reinterpret_cast<uint4*>(txt + c * 16u) = v[r];
-                const uint32_t m = fz_newlines16(v[r]);
+                const uint32_t m = fr_chunk_marks(fz_newlines16(v[r]), &blank);
                 const uint32_t cnt = (uint32_t)__popc(m);
                 my_lines += cnt;
                 marks[r] = m;
-                nl_packed |= cnt << (kFzNlBits * r);
-            } else if (cw < kFzChunksPerWave && c < kFzChunks) {
-                *reinterpret_cast<uint4*>(txt + c * 16u) = v[r];
-                if (p < w1) {
-                    uint32_t m = fz_newlines16(v[r]);
-                    if (p + 16u > a.n) m &= p >= a.n ? 0u : (1u << (a.n - p)) - 1u;  // (nothing behind n is text)
-                    if (p >= counted && p < t1) my_lines += (uint32_t)__popc(m);     // (the block's lines: counted in the span they end in, once)
-                    if (a.open_end && a.n >= p && a.n < p + 16u) m |= 1u << (a.n - p);  // (n itself ends an open last line)
-                    if (p + 16u > w1) m &= (1u << (w1 - p)) - 1u;
-                    if (p < wpos) m &= ~((1u << (wpos - p)) - 1u);                   // (the tail of the line before is no text of this window)
-                    marks[r] = m;
-                    nl_packed |= (uint32_t)__popc(m) << (kFzNlBits * r);
-                }
+                nl_packed |= fr_pack(cnt, r);
+            } else if (p < w1) {
+                uint32_t m = fz_newlines16(v[r]);
+                if (p + 16u > a.n) m &= p >= a.n ? 0u : (1u << (a.n - p)) - 1u;  // (nothing behind n is text)
+                if (p >= counted && p < t1) my_lines += (uint32_t)__popc(m);     // (the block's lines: counted in the span they end in, once)
+                if (a.open_end && a.n >= p && a.n < p + 16u) m |= 1u << (a.n - p);  // (n itself ends an open last line)
+                if (p + 16u > w1) m &= (1u << (w1 - p)) - 1u;
+                if (p < wpos) m &= ~((1u << (wpos - p)) - 1u);                   // (the tail of the line before is no text of this window)
+                m = fr_chunk_marks(m, &blank);
+                marks[r] = m;
+                nl_packed |= fr_pack((uint32_t)__popc(m), r);
             }
         }
+        if (blank && !(ablate & 16u)) my_flags |= kDtokShortLine;  // (16: the measurement that leaves that flag out)
         // (one scan in registers: the wave's count now, the lines' numbers behind the barrier)
         const uint32_t nl_inc = fz_wave_scan(nl_packed);
         const uint32_t nl_wave = fz_last_lane(nl_inc);
-        if (lane == 0) wtot[wave] = (nl_wave & kFzNlMask) + ((nl_wave >> kFzNlBits) & kFzNlMask) + (nl_wave >> (2u * kFzNlBits));
+        if (lane == 0) wtot[wave] = fr_total(nl_wave);
         __syncthreads();
         uint32_t before = 0, total_nl = 0;
 #pragma unroll
@@ -461,23 +463,24 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
         }
         // lines of the window: line k = [ls[k], ls[k + 1] - 1), k < total_nl whole (line 0 of a span's first window only
         // when it starts the text: that window begins in the middle of a line, the others at one)
-        const bool too_many = total_nl + 1u > kFzLines || (a.ablate & (32u | 512u));
+        const bool too_many = total_nl + 1u > kFzLines || (ablate & (32u | 512u));
         if (too_many) {
-            if (!(a.ablate & 512u)) my_flags |= kDtokSpill;
+            if (!(ablate & 512u)) my_flags |= kDtokSpill;
         } else {
             if (tid == 0) ls[0] = (uint16_t)lead;
             uint32_t line = before;  // newlines in front of this wave's chunks
 #pragma unroll
             for (uint32_t r = 0; r < kFzRounds; ++r) {
-                const uint32_t c = wave * kFzChunksPerWave + r * kWave + lane;
-                uint32_t at = line + ((nl_inc >> (kFzNlBits * r)) & kFzNlMask) - (uint32_t)__popc(marks[r]);
+                if (r >= wave_rounds) continue;  // (wave-uniform)
+                const uint32_t c = wave_c0 + r * kWave + lane;
+                uint32_t at = line + fr_unpack(nl_inc, r) - (uint32_t)__popc(marks[r]);
                 uint32_t m = marks[r];
                 while (m) {
                     const uint32_t b = (uint32_t)__ffs((int)m) - 1u;
                     ls[++at] = (uint16_t)(c * 16u + b + 1u);
                     m &= m - 1u;
                 }
-                line += (nl_wave >> (kFzNlBits * r)) & kFzNlMask;
+                line += fr_unpack(nl_wave, r);
             }
         }
         __syncthreads();
@@ -500,7 +503,7 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
             // line's 32 bytes reach into the next line), and its three lowest bits taken: no loop, no indexed array.
             // (The 32 bytes lie inside txt wherever the line starts: 32 bytes of pad behind the last chunk.)
             uint32_t tab[3] = {0, 0, 0}, nt = 0;
-            if (!(a.ablate & 256u)) {
+            if (!(ablate & 256u)) {
                 uint32_t m = fz_tabs32(txt + s);
                 if (e - s < 32u) m &= (1u << (e - s)) - 1u;
                 nt = min((uint32_t)__popc(m), 3u);
@@ -526,7 +529,7 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
                 }
             }
             uint32_t word = 0;
-            if (a.ablate & 16u) {
+            if (ablate & 16u) {
             } else if (nt < 3u) {  // not `qname, flag, rname, _ = line.split('\t', 3)` (align.py:313)
                 my_flags |= kDtokShortLine;
             } else {
@@ -565,7 +568,7 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
             const unsigned char* name = txt + f_rb[k];
             const uint32_t rn = f_rn[k];
             FzProbe probe;
-            if (!(a.ablate & 1u)) probe = fz_probe_begin(a, name, rn);
+            if (!(ablate & 1u)) probe = fz_probe_begin(a, name, rn);
             uint32_t j = k;
             bool found = false;
             while (j > first_line) {
@@ -576,7 +579,7 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
                 }
             }
             bool start;
-            if (a.ablate & 8u)
+            if (ablate & 8u)
                 start = true;
             else if (found)
                 start = f_qn[j] != f_qn[k] || !fz_same(txt + ls[k], txt + ls[j], f_qn[k]);
@@ -586,11 +589,11 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
                 start = true;
             else
                 start = fz_starts_run_slow(a.text, w0 + ls[first_line], txt + ls[k], f_qn[k]);
-            int32_t sid = (a.ablate & 1u) ? (int32_t)(fz_load32(name + 4) % 1000u) : fz_probe_end(a, probe, name, rn, w0 + f_rb[k]);
+            int32_t sid = (ablate & 1u) ? (int32_t)(fz_load32(name + 4) % 1000u) : fz_probe_end(a, probe, name, rn, w0 + f_rb[k]);
             bool excluded = false;
-            if (a.submap && sid >= 0) {
+            if (submap && sid >= 0) {
                 if ((uint32_t)sid < a.n_submap) {
-                    sid = a.submap[sid];
+                    sid = submap[sid];
                     if (sid == kLineExcluded) {  // (`--exclude`: the run goes, all its mates; align.py:47-115)
                         excluded = true;
                         sid = 0;
@@ -623,7 +626,7 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
         uint32_t next = 0u, next_mode = 0u, nc_next = 0u;
         bool more = false, again = false, put_aside = false;
         if (too_many) {
-            if ((a.ablate & (32u | 512u)) && !last_win) {  // (measurement: the loads and the newlines of every window)
+            if ((ablate & (32u | 512u)) && !last_win) {  // (measurement: the loads and the newlines of every window)
                 next = w1;
                 next_mode = 2u;
                 more = true;
@@ -701,7 +704,7 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
                 atomicOr(&info[j], kFiDropped);
             }
             bool dup = false;
-            if (mapped && !excl && !(mk & kFiStart) && !(a.ablate & 2u)) {
+            if (mapped && !excl && !(mk & kFiStart) && !(ablate & 2u)) {
                 bool done = false;
                 for (int32_t j = k; !done; j -= 8) {
                     uint32_t w[8];
@@ -736,10 +739,10 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
             const uint32_t li = (uint32_t)(k - ka);  // (bit li % 64 = lane of word li / 64 of the planes)
             const uint32_t mk = k < kb ? info[k] : 0u;
             const unsigned long long* const mine = planes[kFpFirst + ((mk >> kFiMateShift) & 3u)];
-            if (k < kb && ((mine[li / 64u] >> (li % 64u)) & 1ull) && !(a.ablate & 4u)) {
+            if (k < kb && ((mine[li / 64u] >> (li % 64u)) & 1ull) && !(ablate & 4u)) {
                 uint32_t pos = 0, size = 1;
                 bool dropped = (mk & kFiStart) && (mk & kFiDropped);
-                if (!(a.ablate & (2u | 128u))) {
+                if (!(ablate & (2u | 128u))) {
                     // (the head and the end of the run from the starts' plane, the first lines of this mate between them
                     // counted; the run's first line knows whether the run is dropped)
                     const FpRead r = fp_read(planes[kFpStart], mine, li, (uint32_t)(kb - ka));
@@ -757,7 +760,8 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
                     my_reads += pos == 0u ? 1u : 0u;
                 }
             }
-            // a place in the slice's buffer: ONE LDS atomic per wave (the slices' counts are 16-bit fields of one word)
+            // A place in the slice's buffer: ONE LDS atomic per wave on the buffers' fill itself (the slices' counts are
+            // 16-bit fields of one word), so what comes back are places in the buffers.
             {
                 unsigned long long add = 0;
                 uint32_t mine_before = 0;
@@ -768,22 +772,30 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
                 }
                 if (add) {  // (wave-uniform)
                     unsigned long long base = 0;
-                    if (lane == 0) base = atomicAdd(&newc_packed, add);
+                    if (lane == 0) base = atomicAdd(&fill_packed, add);
                     base = fz_first_lane64(base);
                     at = (uint32_t)(base >> (16u * sl)) & 0xFFFFu;
                     at += mine_before;
                 }
             }
             __syncthreads();
-            const unsigned long long newc = newc_packed;
-            bool full = false;
-            for (uint32_t s2 = 0; s2 < n_streams; ++s2) full |= rcnt[s2] + ((uint32_t)(newc >> (16u * s2)) & 0xFFFFu) > kFzCap;
-            if (full) flush_all(false);  // (uniform: every thread reads the same counters)
-            if (rec) rbuf[sl][rcnt[sl] + at] = word;
-            __syncthreads();
-            if (tid < n_streams) rcnt[tid] += (uint32_t)(newc >> (16u * tid)) & 0xFFFFu;
-            if (tid == 0) newc_packed = 0ull;
-            __syncthreads();
+            // (every thread reads the same word: the fill with this trip's records.  A field above kFzCap -- 0x7BFF more
+            // reaches bit 15, and no field carries: it is at most kFzCap + kFzThreads -- and the buffers leave first as
+            // they were before the trip, `fill`; this trip's places move down by that much, and so does the word.)
+            unsigned long long now = fz_first_lane64(fill_packed);
+            static_assert(kFzCap + 0x7BFFu == 0x7FFFu && 2u * kFzCap + kFzThreads + 0x7BFFu < 0x10000u, "the full test");
+            if ((now + 0x7BFF7BFF7BFF7BFFull) & 0x8000800080008000ull) {  // (uniform, and rare)
+                flush_all(fill, false);
+                at -= (uint32_t)(fill >> (16u * sl)) & 0xFFFFu;
+                now -= fill;  // (field by field: none is below the fill's)
+                if (tid == 0) fill_packed = now;
+            }
+            if (rec) rbuf[sl][at] = word;
+            fill = now;
+            // (Nobody adds to the word before everybody has read it: a window's first trip is behind the barriers of
+            // the window's top, a trip that follows another behind this one.  The same barrier stands between thread
+            // 0's store above and the next add.)
+            if (k0 + (int32_t)kFzThreads < kb) __syncthreads();
         }
         if (!more) break;
         wpos = next;
@@ -801,7 +813,7 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
         const unsigned long long t = ((unsigned long long)lines_w << 32) | reads_w;
         if (lane == 0 && t) atomicAdd(&wg_totals, t);
     }
-    flush_all(true);
+    flush_all(fill, true);
     __syncthreads();
     if (tid == 0) {
         if (wg_totals) __hip_atomic_fetch_add(fz_totals(a.state), wg_totals, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (nothing comes back)
@@ -816,10 +828,14 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
     if (own[0]) {
         __threadfence();
         // (the cursors behind the block, and how far they are from those in front of it: the block's records)
-        if (tid < (uint32_t)kMaxStreams) {
-            const unsigned long long cur = __hip_atomic_load(&a.streams.cursor[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            a.backup_next[tid] = cur;
-            gbase_out[tid] = tid < n_streams ? cur - a.backup_prev[tid] : 0ull;
+        // (the thread's number once more, as a value of its own: addresses made of `tid` up there are not kept in
+        // registers through the windows for this one use -- the kernel has none to spare)
+        uint32_t xt = tid;
+        asm volatile("" : "+v"(xt));
+        if (xt < (uint32_t)kMaxStreams) {
+            const unsigned long long cur = __hip_atomic_load(&a.streams.cursor[xt], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            a.backup_next[xt] = cur;
+            gbase_out[xt] = xt < n_streams ? cur - a.backup_prev[xt] : 0ull;
         }
         __syncthreads();
         if (tid == 0) {

@@ -3523,6 +3523,7 @@ static int dtok_scan_impl(wk_ctx* c, wk_tok* tok, const char* text, int64_t begi
             fa.n = n;
             fa.open_end = open_end ? 1u : 0u;
             const unsigned grid = fused_spans(c, n, &fa.span);
+            if (fa.span % 16u) return fail(c, WK_E_ARG, "spans of the one-kernel tokenizer are multiples of 16 bytes");
             fa.dict8 = c->d_dict2.as<DictSlot8>();
             fa.names16 = c->d_names16.as<uint4>();
             fa.dict_mask = c->dt_dict_mask;
@@ -3788,6 +3789,7 @@ int wk_dtok_scan_emit_begin(wk_ctx* c, wk_tok* tok, const char* text, int64_t be
     fa.n = n;
     fa.open_end = open_end ? 1u : 0u;
     const unsigned grid = fused_spans(c, n, &fa.span);
+    if (fa.span % 16u) return fail(c, WK_E_ARG, "spans of the one-kernel tokenizer are multiples of 16 bytes");
     fa.dict8 = c->d_dict2.as<DictSlot8>();
     fa.names16 = c->d_names16.as<uint4>();
     fa.dict_mask = c->dt_dict_mask;
