@@ -54,6 +54,7 @@
 // kernels on such a block.
 #pragma once
 #include "wk_dtok.hpp"
+#include "wk_dtok_neighbour.hpp"
 #include "wk_dtok_planes.hpp"
 #include "wk_dtok_rounds.hpp"
 
@@ -215,11 +216,25 @@ struct FzProbe {
 };
 __device__ __forceinline__ FzProbe fz_probe_begin(const FusedArgs& a, const unsigned char* name, uint32_t rn) {
     FzProbe p;
-    p.hv = fz_hash(name, rn);
     p.n0 = p.n1 = 0ull;
     if (rn <= 15u) {
-        p.n0 = fz_low_bytes(fz_load64(name), rn);
-        p.n1 = (rn > 8u ? fz_low_bytes(fz_load64(name + 8), rn - 8u) : 0ull) | ((unsigned long long)rn << 56);
+        // (the name's bytes read once, for the hash -- fz_hash(name, rn), written out for at most two words -- and for
+        // the compare with names16; the second word lies inside txt's pad at the latest)
+        const unsigned long long lo = fz_low_bytes(fz_load64(name), rn), hi = rn > 8u ? fz_low_bytes(fz_load64(name + 8), rn - 8u) : 0ull;
+        p.n0 = lo;
+        p.n1 = hi | ((unsigned long long)rn << 56);
+        unsigned long long h = 0xcbf29ce484222325ull ^ ((unsigned long long)rn * 0x9E3779B97F4A7C15ull), v = lo;
+        if (rn >= 8u) {
+            h = (h ^ lo) * 0x100000001b3ull;
+            h ^= h >> 29;
+            v = hi;
+        }
+        h = (h ^ v) * 0x100000001b3ull;
+        h ^= h >> 32;
+        h *= 0x9E3779B97F4A7C15ull;
+        p.hv = h ^ (h >> 29);
+    } else {
+        p.hv = fz_hash(name, rn);
     }
     p.h = (uint32_t)p.hv & a.dict_mask;
     p.slot = reinterpret_cast<const uint2*>(a.dict8)[p.h];
@@ -279,12 +294,13 @@ constexpr uint32_t kFiSubj = (1u << 23) - 1u;   // subject index (all ones: not 
 constexpr uint32_t kFiMateShift = 24;
 constexpr uint32_t kFiMapped = 1u << 26;
 constexpr uint32_t kFiStart = 1u << 27;          // starts a run of equal QNAMEs
-// (bit 28 was "first line of its read (run, mate) that names its subject": that is a bit of the planes now)
+constexpr uint32_t kFiUndecided = 1u << 28;      // (between the line pass and the pass behind it) the lane below could not say whether the line starts a run
 constexpr uint32_t kFiExcl = 1u << 29;           // names a subject of the exclusion set
 constexpr uint32_t kFiDropped = 1u << 30;        // (on the line that starts a run) a line of the run does: the run is dropped whole
 constexpr uint32_t kFiRead = kFiMapped | (3u << kFiMateShift);          // same read of a run: same mate (and mapped)
 constexpr uint32_t kFiKey = kFiRead | kFiSubj;                          // ... and the same subject
 constexpr uint32_t kFzPad = 8;                   // words in front of the lines' words (the duplicate walk reads eight at a time; nothing walks ahead any more)
+constexpr uint32_t kFzEdgeMeta = 4;            // a line's summary at a seam of the line pass: words 0-3 the bytes, this one FnLine::meta
 
 // The 0x80 marks of two words (bits 7, 15, 23, 31 of each) as bits 0-7, the first word's in the low nibble: the second
 // word's marks go between the first one's (bits 4, 12, 20, 28), and one multiplication gathers all eight.  (Mark 8j [+4]
@@ -298,7 +314,8 @@ __device__ __forceinline__ uint32_t fz_newlines16(uint4 v) {
 }
 
 // the tabs among the 32 bytes at p (LDS, any alignment) as the bits of one word
-__device__ __forceinline__ uint32_t fz_tabs32(const unsigned char* p) {
+// (`q0`, `q1`, where given: the first 16 of those bytes, for the neighbour's compare -- wk_dtok_neighbour.hpp)
+__device__ __forceinline__ uint32_t fz_tabs32(const unsigned char* p, unsigned long long* q0 = nullptr, unsigned long long* q1 = nullptr) {
     unsigned long long w[4];
 #pragma unroll
     for (uint32_t i = 0; i < 4; ++i) w[i] = fz_load64(p + 8u * i);
@@ -306,13 +323,20 @@ __device__ __forceinline__ uint32_t fz_tabs32(const unsigned char* p) {
 #pragma unroll
     for (uint32_t i = 0; i < 4; ++i)
         m |= fz_octet(fz_marks32((uint32_t)w[i], 0x09090909u), fz_marks32((uint32_t)(w[i] >> 32), 0x09090909u)) << (8u * i);
+    if (q0) {
+        *q0 = w[0];
+        *q1 = w[1];
+    }
     return m;
 }
 
 __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu(6, 6))) dtok_fused_kernel(FusedArgs a) {
     __shared__ __attribute__((aligned(16))) unsigned char txt[kFzChunks * 16 + 32];
     __shared__ uint16_t ls[kFzLines + 2];                                    // line starts (window offsets); ls[k + 1] - 1 = the newline of line k
-    __shared__ uint16_t f_qn[kFzLines], f_rb[kFzLines], f_rn[kFzLines];      // QNAME length, RNAME offset and length
+    __shared__ uint16_t f_qn[kFzLines];                                      // QNAME length (the lines the lane below does not settle, and a run put aside)
+    // The line pass's 64-line groups at their seams (wk_dtok_neighbour.hpp): [g][0] the summary of group g's first line,
+    // [g][1] that of the line in front of it -- group g - 1's last; nothing in front of group 0.  Five words of eight.
+    __shared__ __attribute__((aligned(16))) uint32_t edge[kFzLines / kWave + 1][2][8];
     __shared__ __attribute__((aligned(16))) uint32_t info_[kFzPad + kFzCarry + kFzLines + kFzPad + 8];
     __shared__ uint32_t carry[kFzCarry];                                     // the words of a run's lines seen in windows before this one
     __shared__ unsigned long long planes[kFpPlanes][kFpWords];               // the owned lines as bits: run starts, first lines per mate (wk_dtok_planes.hpp)
@@ -339,6 +363,7 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
     if (tid < 4u) reinterpret_cast<uint32_t*>(txt + kFrTailChunk * 16u)[tid] = 0u;  // (no wave's chunk and never text: wk_dtok_rounds.hpp)
     if (tid == 0) wg_flags = 0u;
     if (tid == 0) wg_totals = 0ull;
+    if (tid == 0) edge[0][1][kFzEdgeMeta] = 0u;  // (its `meta`: no line in front of group 0; never written again)
     uint32_t my_flags = 0, my_reads = 0, my_lines = 0;
     const uint32_t text_end = a.n + (a.open_end ? 1u : 0u);  // (a text without a last newline: as if one followed)
 
@@ -496,118 +521,182 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
         const uint32_t n_lines = too_many ? 0u : total_nl;  // whole lines: [first_line, n_lines)
         if (tid == 0 && first_line) info[0] = 0u;
 
-        // ---- a thread per line: three tabs, FLAG, RNAME ----
-        for (uint32_t k = first_line + tid; k < n_lines; k += kFzThreads) {
-            const uint32_t s = ls[k], e = (uint32_t)ls[k + 1] - 1u;
-            // The tabs of the line's first 32 bytes as one mask, the bits at or behind the line's end cleared (a short
-            // line's 32 bytes reach into the next line), and its three lowest bits taken: no loop, no indexed array.
-            // (The 32 bytes lie inside txt wherever the line starts: 32 bytes of pad behind the last chunk.)
-            uint32_t tab[3] = {0, 0, 0}, nt = 0;
-            if (!(ablate & 256u)) {
-                uint32_t m = fz_tabs32(txt + s);
-                if (e - s < 32u) m &= (1u << (e - s)) - 1u;
-                nt = min((uint32_t)__popc(m), 3u);
-                tab[0] = s + (uint32_t)__ffs((int)m) - 1u;
-                m &= m - 1u;
-                tab[1] = s + (uint32_t)__ffs((int)m) - 1u;
-                m &= m - 1u;
-                tab[2] = s + (uint32_t)__ffs((int)m) - 1u;  // (the first `nt` of the three are tabs; the others are not looked at)
-                // fewer than three and the line goes on: a QNAME or an RNAME of some length (rare on the texts measured)
-                for (uint32_t p = s + 32u; nt < 3u && p < e; p += 32u) {
-                    m = fz_tabs32(txt + p);
-                    if (e - p < 32u) m &= (1u << (e - p)) - 1u;
-                    for (; m && nt < 3u; m &= m - 1u) {
-                        const uint32_t q = p + (uint32_t)__ffs((int)m) - 1u;
-                        if (nt == 0u)
-                            tab[0] = q;
-                        else if (nt == 1u)
-                            tab[1] = q;
-                        else
-                            tab[2] = q;
-                        ++nt;
+        // ---- a thread per line: three tabs, FLAG, RNAME; its subject; does it start a run? ----
+        // Line k is lane (k - first_line) % 64's, so the line before it is the lane below's: a mapped line at or behind
+        // t0 learns from that lane's summary whether it starts a run (wk_dtok_neighbour.hpp) while the dictionary slot
+        // of its subject is on its way.  What the neighbour does not settle -- it is unmapped, the QNAMEs are longer
+        // than 16 bytes and agree that far, the window's first line; and every wave's first lane, whose neighbour is
+        // another wave's -- is marked kFiUndecided and settled behind the barrier.  (Every lane takes every trip: the
+        // lanes exchange words.  The lines behind the last owned run are looked up for nothing: the rest of one run,
+        // and once per span what the kFzFwd bytes behind it hold.)
+        for (uint32_t k0 = first_line; k0 < n_lines; k0 += kFzThreads) {
+            const uint32_t k = k0 + tid;
+            const bool has = k < n_lines;
+            uint32_t word = 0, s = 0, qn = 0, rb = 0, rn = 0;
+            unsigned long long q0 = 0ull, q1 = 0ull;
+            if (has) {
+                s = ls[k];
+                const uint32_t e = (uint32_t)ls[k + 1] - 1u;
+                // The tabs of the line's first 32 bytes as one mask, the bits at or behind the line's end cleared (a short
+                // line's 32 bytes reach into the next line), and its three lowest bits taken: no loop, no indexed array.
+                // (The 32 bytes lie inside txt wherever the line starts: 32 bytes of pad behind the last chunk.)
+                uint32_t tab[3] = {0, 0, 0}, nt = 0;
+                if (!(ablate & 256u)) {
+                    uint32_t m = fz_tabs32(txt + s, &q0, &q1);
+                    if (e - s < 32u) m &= (1u << (e - s)) - 1u;
+                    nt = min((uint32_t)__popc(m), 3u);
+                    tab[0] = s + (uint32_t)__ffs((int)m) - 1u;
+                    m &= m - 1u;
+                    tab[1] = s + (uint32_t)__ffs((int)m) - 1u;
+                    m &= m - 1u;
+                    tab[2] = s + (uint32_t)__ffs((int)m) - 1u;  // (the first `nt` of the three are tabs; the others are not looked at)
+                    // fewer than three and the line goes on: a QNAME or an RNAME of some length (rare on the texts measured)
+                    for (uint32_t p = s + 32u; nt < 3u && p < e; p += 32u) {
+                        m = fz_tabs32(txt + p);
+                        if (e - p < 32u) m &= (1u << (e - p)) - 1u;
+                        for (; m && nt < 3u; m &= m - 1u) {
+                            const uint32_t q = p + (uint32_t)__ffs((int)m) - 1u;
+                            if (nt == 0u)
+                                tab[0] = q;
+                            else if (nt == 1u)
+                                tab[1] = q;
+                            else
+                                tab[2] = q;
+                            ++nt;
+                        }
+                    }
+                }
+                if (ablate & 16u) {
+                } else if (nt < 3u) {  // not `qname, flag, rname, _ = line.split('\t', 3)` (align.py:313)
+                    my_flags |= kDtokShortLine;
+                } else {
+                    const uint32_t fl = tab[1] - tab[0] - 1u;
+                    const unsigned long long fw = fz_load64(txt + tab[0] + 1u);
+                    uint32_t flag = 0;
+                    bool digits = fl >= 1u && fl <= 6u;
+                    for (uint32_t i = 0; i < fl && i < 6u; ++i) {
+                        const uint32_t d = ((uint32_t)(fw >> (8u * i)) & 0xFFu) - (uint32_t)'0';
+                        digits &= d <= 9u;
+                        flag = flag * 10u + d;
+                    }
+                    rb = tab[1] + 1u;
+                    rn = tab[2] - rb;
+                    if (!digits) {
+                        my_flags |= kDtokShortLine;
+                    } else if (rn == 1u && txt[rb] == '*') {
+                        // unmapped: skipped before anything else (align.py:318-319)
+                    } else {
+                        const uint32_t mate = (flag >> 6) & 3u;
+                        if (mate == 3u) my_flags |= kDtokBothMates;
+                        word = kFiMapped | (mate << kFiMateShift);
+                        qn = tab[0] - s;
+                        f_qn[k] = (uint16_t)qn;
                     }
                 }
             }
-            uint32_t word = 0;
-            if (ablate & 16u) {
-            } else if (nt < 3u) {  // not `qname, flag, rname, _ = line.split('\t', 3)` (align.py:313)
-                my_flags |= kDtokShortLine;
-            } else {
-                const uint32_t fl = tab[1] - tab[0] - 1u;
-                const unsigned long long fw = fz_load64(txt + tab[0] + 1u);
-                uint32_t flag = 0;
-                bool digits = fl >= 1u && fl <= 6u;
-                for (uint32_t i = 0; i < fl && i < 6u; ++i) {
-                    const uint32_t d = ((uint32_t)(fw >> (8u * i)) & 0xFFu) - (uint32_t)'0';
-                    digits &= d <= 9u;
-                    flag = flag * 10u + d;
-                }
-                const uint32_t rb = tab[1] + 1u, rn = tab[2] - rb;
-                if (!digits) {
-                    my_flags |= kDtokShortLine;
-                } else if (rn == 1u && txt[rb] == '*') {
-                    // unmapped: skipped before anything else (align.py:318-319)
-                } else {
-                    const uint32_t mate = (flag >> 6) & 3u;
-                    if (mate == 3u) my_flags |= kDtokBothMates;
-                    word = kFiMapped | (mate << kFiMateShift);
-                    f_qn[k] = (uint16_t)(tab[0] - s);
-                    f_rb[k] = (uint16_t)rb;
-                    f_rn[k] = (uint16_t)rn;
-                }
+            // (every lane again)  The subject of a mapped line at or behind t0 (only a first window has lines in front
+            // of it): the first slot is asked for here and looked at behind the exchange.
+            const bool mapped = (word & kFiMapped) != 0u, look = mapped && w0 + s >= t0;
+            const unsigned char* const name = txt + rb;
+            FzProbe probe;
+            if (look && !(ablate & 1u)) probe = fz_probe_begin(a, name, rn);
+            // the line's summary one lane up; lane 0 takes "no line" and asks the group's seam behind the barrier
+            const FnLine me = has ? fn_line(mapped, qn, q0, q1) : fn_no_line();
+            FnLine prev;
+            prev.meta = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)me.meta, 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
+#pragma unroll
+            for (uint32_t i = 0; i < 4; ++i) prev.b[i] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)me.b[i], 0x138, 0xF, 0xF, false);
+            const uint32_t verdict = (ablate & 8u) ? (uint32_t)kFnStarts : (uint32_t)fn_verdict(prev, me);
+            if (lane == 0 || lane == kWave - 1u) {
+                uint32_t* const to = lane == 0 ? edge[(k0 - first_line) / kWave + wave][0] : edge[(k0 - first_line) / kWave + wave + 1u][1];
+                *reinterpret_cast<uint4*>(to) = make_uint4(me.b[0], me.b[1], me.b[2], me.b[3]);
+                to[kFzEdgeMeta] = me.meta;
             }
-            info[k] = word;
+            const bool start = look && verdict == kFnStarts;
+            if (look) {
+                int32_t sid = (ablate & 1u) ? (int32_t)(fz_load32(name + 4) % 1000u) : fz_probe_end(a, probe, name, rn, w0 + rb);
+                bool excluded = false;
+                if (submap && sid >= 0) {
+                    if ((uint32_t)sid < a.n_submap) {
+                        sid = submap[sid];
+                        if (sid == kLineExcluded) {  // (`--exclude`: the run goes, all its mates; align.py:47-115)
+                            excluded = true;
+                            sid = 0;
+                        }
+                    } else {  // (a name the host has not mapped yet: the block is done again)
+                        my_flags |= kDtokSpill;
+                        sid = -1;
+                    }
+                }
+                word |= (start ? kFiStart : 0u) | (verdict == kFnUndecided ? kFiUndecided : 0u) | (excluded ? kFiExcl : 0u) |
+                        (sid < 0 ? kFiSubj : ((uint32_t)sid & kFiSubj));
+            }
+            if (has) info[k] = word;  // (the line's whole word, once)
+            // The window's run starts: k rises with the lane, so a wave's first and last are its ballots' lowest and
+            // highest bits -- one lane tells own[].
+            const unsigned long long b_all = __ballot(start), b_in = __ballot(start && w0 + s < t1), b_out = b_all & ~b_in;
+            if (lane == 0 && b_all) {
+                if (b_in) atomicMin(&own[0], k + (uint32_t)__builtin_ctzll(b_in));
+                if (b_out) atomicMin(&own[1], k + (uint32_t)__builtin_ctzll(b_out));
+                atomicMax(&own[2], k + 63u - (uint32_t)__builtin_clzll(b_all));
+            }
         }
         __syncthreads();
-
-        // ---- a mapped line at or behind t0: does it start a run (QNAME against the mapped line before it)?  Its subject?
-        // (the dictionary slot is on its way while the QNAMEs are compared; the lines behind the last owned run are
-        // looked up for nothing: the rest of one run, and once per span what the kFzFwd bytes behind it hold)
-        for (uint32_t k = first_line + tid; k < n_lines; k += kFzThreads) {
-            if (!(info[k] & kFiMapped) || w0 + ls[k] < t0) continue;  // (only in a first window: the others begin behind t0)
-            const unsigned char* name = txt + f_rb[k];
-            const uint32_t rn = f_rn[k];
-            FzProbe probe;
-            if (!(ablate & 1u)) probe = fz_probe_begin(a, name, rn);
-            uint32_t j = k;
-            bool found = false;
-            while (j > first_line) {
-                --j;
-                if (info[j] & kFiMapped) {
-                    found = true;
-                    break;
+        // ---- what the lane below did not settle: the seams between the groups, then the search back ----
+        // (a wave's first lane: the same verdict from its group's seam, one read and no loop.  The rest is what every
+        // mapped line used to do: the mapped line before it searched for, the QNAMEs compared byte by byte -- behind a
+        // wave-uniform branch that text of short QNAMEs and few unmapped lines enters for a span's first window only.)
+        for (uint32_t k0 = first_line; k0 < n_lines; k0 += kFzThreads) {
+            const uint32_t k = k0 + tid;
+            const uint32_t mk = k < n_lines ? info[k] : 0u;
+            bool und = (mk & kFiUndecided) != 0u, start = false;
+            if (lane == 0 && und) {
+                const uint32_t g = (k0 - first_line) / kWave + wave;  // (g = 0: the window's first line)
+                FnLine before, me;
+#pragma unroll
+                for (uint32_t i = 0; i < 4; ++i) {
+                    before.b[i] = edge[g][1][i];
+                    me.b[i] = edge[g][0][i];
+                }
+                before.meta = edge[g][1][kFzEdgeMeta];
+                me.meta = edge[g][0][kFzEdgeMeta];
+                const FnVerdict v = fn_verdict(before, me);
+                und = v == kFnUndecided;
+                start = v == kFnStarts;
+                // (the line the window before stopped at, or the first of the text: it starts a run, no search needed)
+                if (g == 0u && nc == 0u && (mode == 1u || wpos == 0u)) {
+                    und = false;
+                    start = true;
                 }
             }
-            bool start;
-            if (ablate & 8u)
-                start = true;
-            else if (found)
-                start = f_qn[j] != f_qn[k] || !fz_same(txt + ls[k], txt + ls[j], f_qn[k]);
-            else if (nc)  // (the mapped line before is the carried run's last)
-                start = f_qn[k] != cq_len || !fz_same(txt + ls[k], a.text + cq_pos, cq_len);
-            else if (mode == 1u || wpos == 0u)  // (the line the window before stopped at, or the first of the text)
-                start = true;
-            else
-                start = fz_starts_run_slow(a.text, w0 + ls[first_line], txt + ls[k], f_qn[k]);
-            int32_t sid = (ablate & 1u) ? (int32_t)(fz_load32(name + 4) % 1000u) : fz_probe_end(a, probe, name, rn, w0 + f_rb[k]);
-            bool excluded = false;
-            if (submap && sid >= 0) {
-                if ((uint32_t)sid < a.n_submap) {
-                    sid = submap[sid];
-                    if (sid == kLineExcluded) {  // (`--exclude`: the run goes, all its mates; align.py:47-115)
-                        excluded = true;
-                        sid = 0;
+            if (__ballot(und) != 0ull) {  // (wave-uniform)
+                if (und) {
+                    uint32_t j = k;
+                    bool found = false;
+                    while (j > first_line) {
+                        --j;
+                        if (info[j] & kFiMapped) {
+                            found = true;
+                            break;
+                        }
                     }
-                } else {  // (a name the host has not mapped yet: the block is done again)
-                    my_flags |= kDtokSpill;
-                    sid = -1;
+                    if (found)
+                        start = f_qn[j] != f_qn[k] || !fz_same(txt + ls[k], txt + ls[j], f_qn[k]);
+                    else if (nc)  // (the mapped line before is the carried run's last)
+                        start = f_qn[k] != cq_len || !fz_same(txt + ls[k], a.text + cq_pos, cq_len);
+                    else if (mode == 1u || wpos == 0u)  // (the line the window before stopped at, or the first of the text)
+                        start = true;
+                    else
+                        start = fz_starts_run_slow(a.text, w0 + ls[first_line], txt + ls[k], f_qn[k]);
                 }
             }
-            // (this thread's own word; the others look at its mapped bit only)
-            info[k] |= (start ? kFiStart : 0u) | (excluded ? kFiExcl : 0u) | (sid < 0 ? kFiSubj : ((uint32_t)sid & kFiSubj));
-            if (start) {
-                atomicMin(&own[w0 + ls[k] < t1 ? 0 : 1], k);
-                atomicMax(&own[2], k);
+            if (mk & kFiUndecided) {
+                // (this thread's own word; the others look at its mapped bit only)
+                info[k] = (mk & ~kFiUndecided) | (start ? kFiStart : 0u);
+                if (start) {
+                    atomicMin(&own[w0 + ls[k] < t1 ? 0 : 1], k);
+                    atomicMax(&own[2], k);
+                }
             }
         }
         __syncthreads();
