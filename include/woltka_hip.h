@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define WK_ABI_VERSION 2
+#define WK_ABI_VERSION 3
 
 /* error codes */
 #define WK_OK 0
@@ -525,6 +525,51 @@ int wk_dtok_stage_hits_append(wk_ctx* ctx, const int32_t* genome_of_subject,
                               const wk_job* jobs, int32_t n_jobs,
                               int64_t* n_reads, int64_t* n_hits, int* status,
                               int* may_wait);
+
+/* Demultiplexing on the device (csrc/wk_demux.hpp; workflow.demultiplex,
+ * workflow.py:886-907): the sample of a read is its id up to the first '_'
+ * when something follows it (a mate suffix counts), '' otherwise.
+ *   wk_demux_begin     on != 0: the sample table is cleared and blocks of the
+ *                      plain flavour may be staged by wk_dtok_stage_reads;
+ *                      0: the table is given up.
+ *   wk_demux_pending   behind a wk_dtok_scan of the plain flavour (status 0):
+ *                      run starts, the subject map and the exclusion set
+ *                      (wk_dtok_subject_map), then the lookup of every
+ *                      emitted read's sample.  *n = the samples the table does
+ *                      not hold yet, *n_bytes = the bytes of their names.
+ *                      With off / len / blob given (cap >= *n, blob_cap >=
+ *                      *n_bytes) a second call copies them out: in order of
+ *                      the first read that brought them, name k =
+ *                      blob[off[k], off[k] + len[k]).  *status != 0: the
+ *                      block is the host tokenizer's (bit 0: more samples
+ *                      than the table holds).
+ *   wk_demux_register  appends n names (name k = blob[off[k], off[k + 1])) to
+ *                      the table; their ids follow those registered before.
+ *                      group[0, n_total) = the group id of every sample of
+ *                      the table (-1: dropped by the whitelist), to be given
+ *                      again whenever the groups are numbered anew (n = 0).
+ *   wk_dtok_stage_reads the scanned block as the staged classify chunk
+ *                      (what wk_chunk_stage leaves: subject indices, a set per
+ *                      read, a group per read), reads in the order the parser
+ *                      yields them; wk_classify_staged follows.  *status != 0:
+ *                      nothing is staged, the host tokenizer takes the block
+ *                      (a read of more than WK_MAX_K subjects).
+ *   wk_demux_fetch     group[0, n_reads) of the chunk staged last (null: not
+ *                      wanted) and met[0, n_samples): 1 for every sample that
+ *                      a read of that chunk with a group belongs to.
+ * wk_set_option "demux_hash_mask" (AND-ed into every hash, 0: none) and
+ * "demux_max_samples" (0: 65536) are for tests; set them before
+ * wk_demux_begin. */
+int wk_demux_begin(wk_ctx* ctx, int on);
+int wk_demux_pending(wk_ctx* ctx, int64_t* off, int32_t* len, int32_t cap,
+                     int32_t* n, char* blob, int64_t blob_cap,
+                     int64_t* n_bytes, int* status);
+int wk_demux_register(wk_ctx* ctx, const char* blob, const int64_t* off,
+                      int32_t n, const int32_t* group, int32_t n_total);
+int wk_dtok_stage_reads(wk_ctx* ctx, int64_t* n_reads, int64_t* n_records,
+                        int* status);
+int wk_demux_fetch(wk_ctx* ctx, int32_t* group, int64_t group_cap,
+                   unsigned char* met, int32_t met_cap);
 
 /* Convenience: stage + classify in one call from host buffers. */
 int wk_classify_chunk(wk_ctx* ctx, const wk_job* jobs, int32_t n_jobs,

@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get('WOLTKA_HIP_LIB') or os.path.join(
     _HERE, 'libwoltka_hip.so')
 
 # constants mirrored from include/woltka_hip.h
-ABI_VERSION = 2
+ABI_VERSION = 3
 OK, E_HIP, E_ARG, E_STATE, E_CAPACITY, E_RANGE, E_TABLE_FULL = (
     0, -1, -2, -3, -4, -5, -6)
 KEY_FEATURE_BITS, KEY_GROUP_BITS, KEY_K_BITS, KEY_JOB_BITS = 28, 21, 12, 3
@@ -63,6 +63,8 @@ SYMBOLS = (
     'wk_dtok_readmap',
     'wk_dtok_readmap_fetch', 'wk_strata_load', 'wk_strata_labels',
     'wk_strata_groups', 'wk_strata_clear',
+    'wk_demux_begin', 'wk_demux_pending', 'wk_demux_register',
+    'wk_dtok_stage_reads', 'wk_demux_fetch',
     'wk_tok_subjects',
     'wk_tok_new_subjects', 'wk_tok_fetch_groups', 'wk_tok_strata_clear',
     'wk_tok_strata_load', 'wk_tok_strata_labels', 'wk_tok_strata_select',
@@ -243,6 +245,15 @@ def load_library():
         'wk_strata_labels': (C.c_int, [p, i32p, i64p, i32p, C.c_int32, i32p]),
         'wk_strata_groups': (C.c_int, [p, i32p, i32p, C.c_int32]),
         'wk_strata_clear': (C.c_int, [p]),
+        'wk_demux_begin': (C.c_int, [p, C.c_int]),
+        'wk_demux_pending': (C.c_int, [p, i64p, i32p, C.c_int32, i32p,
+                                       C.c_void_p, C.c_int64, i64p,
+                                       C.POINTER(C.c_int)]),
+        'wk_demux_register': (C.c_int, [p, C.c_char_p, i64p, C.c_int32, i32p,
+                                        C.c_int32]),
+        'wk_dtok_stage_reads': (C.c_int, [p, i64p, i64p, C.POINTER(C.c_int)]),
+        'wk_demux_fetch': (C.c_int, [p, i32p, C.c_int64, C.c_void_p,
+                                     C.c_int32]),
         'wk_tok_subjects': (C.c_int, [p, i32p, i32p, i64p]),
         'wk_tok_new_subjects': (C.c_int, [p, C.c_char_p, i32p]),
         'wk_tok_fetch_groups': (C.c_int, [p, i32p]),
@@ -956,6 +967,63 @@ class Context:
 
     def strata_clear(self):
         self._check(self._lib.wk_strata_clear(self._h))
+
+    # -- demultiplexing on the device (csrc/wk_demux.hpp) -------------------
+    def demux_begin(self, on=True):
+        """Clear the device's sample table; ``on``: blocks of the plain
+        flavour may be staged by ``dtok_stage_reads`` from now on."""
+        self._check(self._lib.wk_demux_begin(self._h, int(bool(on))))
+
+    def demux_pending(self):
+        """The samples of the block scanned last that the table does not
+        hold yet.  Returns (status, names as bytes in order of the first read
+        that brought them); status != 0: the host tokenizer takes the block
+        (bit 0: more samples than the table holds)."""
+        n, nb, st = C.c_int32(0), C.c_int64(0), C.c_int(1)
+        self._check(self._lib.wk_demux_pending(
+            self._h, None, None, 0, C.byref(n), None, 0, C.byref(nb),
+            C.byref(st)))
+        if st.value != 0 or n.value == 0:
+            return st.value, []
+        off = np.empty(n.value, dtype=np.int64)
+        ln = np.empty(n.value, dtype=np.int32)
+        blob = np.empty(max(nb.value, 1), dtype=np.uint8)
+        self._check(self._lib.wk_demux_pending(
+            self._h, _ptr(off, C.c_int64), _ptr(ln, C.c_int32), off.size,
+            C.byref(n), C.c_void_p(blob.ctypes.data), blob.size, C.byref(nb),
+            C.byref(st)))
+        return st.value, [blob[o:o + k].tobytes()
+                          for o, k in zip(off.tolist(), ln.tolist())]
+
+    def demux_register(self, names, groups):
+        """Append ``names`` (bytes) to the sample table; ``groups``: the
+        group id of every sample the table then holds (-1: dropped)."""
+        off = np.zeros(len(names) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(x) for x in names], dtype=np.int64)
+        groups = _arr(groups, np.int32)
+        self._check(self._lib.wk_demux_register(
+            self._h, b''.join(names), _ptr(off, C.c_int64), len(names),
+            _ptr(groups, C.c_int32), groups.size))
+
+    def dtok_stage_reads(self):
+        """The scanned block (plain flavour, behind ``demux_pending``) as
+        the staged classify chunk with a group per read.  Returns (status,
+        reads, records)."""
+        a, b, st = C.c_int64(0), C.c_int64(0), C.c_int(1)
+        self._check(self._lib.wk_dtok_stage_reads(
+            self._h, C.byref(a), C.byref(b), C.byref(st)))
+        return st.value, a.value, b.value
+
+    def demux_fetch(self, n_samples, n_reads=None):
+        """(met bytes of the ``n_samples`` samples, groups of the
+        ``n_reads`` reads of the chunk staged last or None)."""
+        met = np.zeros(n_samples, dtype=np.uint8)
+        group = None if n_reads is None else np.empty(n_reads, dtype=np.int32)
+        self._check(self._lib.wk_demux_fetch(
+            self._h, None if group is None else _ptr(group, C.c_int32),
+            0 if group is None else group.size,
+            C.c_void_p(met.ctypes.data) if met.size else None, met.size))
+        return met, group
 
     def ordinal_hit_offsets(self, n_hits):
         """Offsets of every hit's genes in the staged gene lists

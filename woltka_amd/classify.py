@@ -58,6 +58,26 @@ def cover_on_device(fmt, exclude=False, demux=False, strata=False,
                 and n_subjects <= COVER_MAX_SUBJECTS)
 
 
+def demux_on_device(native_demux, fmt, coords=False, sizes=False, n_jobs=1,
+                    replay=False):
+    """Does a file that is demultiplexed keep the device text route, the
+    sample of every read decided on the device (csrc/wk_demux.hpp,
+    `_run_ddemux`)?  ``native_demux``: `--demux` (or a single-file input)
+    without a strata map, read maps or subject coverage; plain classification
+    (not ``coords``) of SAM, BLAST tabular, PAF or simple-map text, with any
+    job set of at most `MAX_JOBS` jobs (``n_jobs``), without `--sizes`, and
+    not during the replay pass (``replay``: it wants the assignments on the
+    host).  Whether the text can be read block by block -- a plain file or a
+    byte range of one, a gzip file this package inflates itself -- is for
+    `native_chunks` to see.  ``WOLTKA_NO_DDEMUX=1`` (like
+    ``WOLTKA_NO_DTOK=1``) keeps every file on the host route."""
+    if os.environ.get('WOLTKA_NO_DDEMUX') or os.environ.get('WOLTKA_NO_DTOK'):
+        return False
+    return bool(native_demux and not coords and not sizes and not replay
+                and fmt in ('sam', 'b6o', 'paf', 'map')
+                and 1 <= n_jobs <= nat.MAX_JOBS)
+
+
 class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
              Folding):
     """One classification job on one GPU.
@@ -182,6 +202,11 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
         self._tok_genome = np.empty(0, dtype=np.int32)
         self._tok_cover = np.empty(0, dtype=np.int64)
         self._dcover = None         # the `Coverage` of the file on the device text route (`--outcov`)
+        # demultiplexing on the device (csrc/wk_demux.hpp)
+        self._ddemux = None         # (whitelist or None,) while a file is read that way
+        self._dx_names = None       # the device's sample table: slot -> name (None: not begun)
+        self._dx_key = None         # (epoch, samples) the device holds groups for
+        self._dx_full = False       # the table refused a block of this file: the rest on the host
         self._cv_cover, self._cv_sample = None, None    # whose ranges the device's coverage pile holds
         self._cv_open = False
         self._ring, self._ring_prev = None, None    # packed-record staging
@@ -361,7 +386,8 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
                       want_names, trimsub=None, want_groups=False,
                       want_strings=True, want_samples=False, cover=None,
                       fmt='sam', part=None, words=False, dmaps=None,
-                      keep_empty=False, words_dev=False, dcover=False):
+                      keep_empty=False, words_dev=False, dcover=False,
+                      ddemux=None):
         """SAM text -> packed chunks through the native tokenizer.  Yields
         (reads or None, packed, strata ids, name descriptors, sample ids,
         ranges) where packed = (subj, qoff) of subject indices, or for
@@ -373,7 +399,9 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
         sample changes and at the end (`cover_flush`).
         ``keep_empty``: hits of aligned length 0 stay in the arrays
         (`regroup_hits` counts them where ordinal.py:222 does, then drops
-        them)."""
+        them).  ``ddemux`` (`demux_on_device`): (whitelist or None,) -- the
+        samples are told on the device and the blocks counted as CSR chunks
+        there (`_run_ddemux`)."""
         from .align import native_sam_blocks
         if self.tok is None:
             # (a tokenizer whose dictionary was filled from this file's first
@@ -396,10 +424,14 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
         # (`--exclude`: the plain flavour's kernels drop the runs that hit a
         # name of the set; not with read maps, not the "ex" parsers' way)
         dcover = bool(dcover and cover is not None and not ordinal)
-        if (words or words_dev or device_ex or dmaps or dcover) and (
+        ddemux = ddemux if (ddemux is not None and want_samples and
+                            not ordinal and cover is None) else None
+        if (words or words_dev or device_ex or dmaps or dcover or
+                ddemux is not None) and (
                 fmt in ('sam', 'b6o', 'paf') or (fmt == 'map' and
                                                  not ordinal)) and \
-                (not exclude or ((words or words_dev) and not dmaps)) and \
+                (not exclude or ((words or words_dev or ddemux is not None)
+                                 and not dmaps)) and \
                 not os.environ.get('WOLTKA_NO_DTOK'):
             from .align import _parallel_reader, part_range
             from .file import GunzipStream
@@ -424,6 +456,20 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
                 self._dmaps = dmaps if not (words or device_ex or dcover) \
                     else None
                 self._dcover = cover if dcover else None
+                self._ddemux = ddemux
+                if ddemux is not None:
+                    # (the reader started before the hierarchy was read is
+                    # not taken under `--demux`: the engine's own reader, as
+                    # for a file whose turn has come)
+                    from .routes.device_text import drop_text_ahead
+                    drop_text_ahead()
+                    # (six kernels and a lookup per block: neither the
+                    # one-kernel tokenizer nor scan and emission in one wait)
+                    self._spec = False
+                    self._dx_full = False
+                    if self._dx_names is None:
+                        self.ctx.demux_begin(True)
+                        self._dx_names, self._dx_key = [], None
                 self.ctx.dtok_keep_reads(self._dmaps is not None)
                 self._dfmt = fmt
                 self._dtrimsub = trimsub if not ordinal else None
@@ -446,6 +492,7 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
                 finally:
                     self._dmaps = None
                     self._dcover = None
+                    self._ddemux = None
                     if getattr(self.ctx, '_h', None):   # (still open)
                         self.ctx.dtok_keep_reads(False)
                 return
@@ -674,6 +721,7 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
     ROUTE_OF = {'dtok': '_run_dtok',        # text scanned on the device -> packed records (routes/device_text.py)
                 'dcover': '_run_dcover',    # ... for the "ex" parsers under `--outcov`: ranges to the coverage pile, then the same
                 'dhits': '_run_dhits',      # text scanned on the device -> coord-match hits
+                'ddemux': '_run_ddemux',    # text scanned on the device -> demultiplexed CSR chunk, counted by the general evaluator
                 'words': '_run_words'}      # packed records of the host tokenizer (routes/words.py)
 
     def _run_general(self, data, reads, subque, sample_of, strata_of, trimsub,

@@ -61,11 +61,12 @@ struct StrataArgs {
     uint32_t* state;                 // [0] flags [1] pairs [2] labels
 };
 
-// streaming 64-bit hash of a byte string (8 bytes per round, FNV-style mixing, avalanche at the end)
+// streaming 64-bit hash of a byte string (8 bytes per round, FNV-style mixing, avalanche at the end); the host hashes
+// the names it puts into a device table with the same code
 struct NameHash {
     unsigned long long h = 0xcbf29ce484222325ull, acc = 0;
     uint32_t k = 0, n = 0;
-    __device__ __forceinline__ void put(unsigned char b) {
+    __host__ __device__ __forceinline__ void put(unsigned char b) {
         acc |= (unsigned long long)b << (8u * k);
         ++n;
         if (++k == 8u) {
@@ -75,7 +76,7 @@ struct NameHash {
             k = 0;
         }
     }
-    __device__ __forceinline__ unsigned long long done() {
+    __host__ __device__ __forceinline__ unsigned long long done() {
         h = (h ^ acc) * 0x100000001b3ull;
         h ^= (unsigned long long)n * 0x9E3779B97F4A7C15ull;
         h ^= h >> 32;

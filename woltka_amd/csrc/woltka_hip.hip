@@ -23,6 +23,7 @@
 #include "wk_cover.hpp"
 #include "wk_device.hpp"
 #include "wk_dtok.hpp"
+#include "wk_demux.hpp"
 #include "wk_dtok_fused.hpp"
 #include "wk_free.hpp"
 #include "wk_ordinal.hpp"
@@ -408,6 +409,22 @@ struct wk_ctx {
     uint32_t s_n = 0, s_n_lines = 0, s_mask = 0;
     bool s_ready = false;   // wk_strata_load built the tables
     bool s_use = false;     // wk_strata_groups gave the labels their groups: wk_dtok_stage_hits joins
+    // demultiplexing on the device (wk_demux.hpp): the sample table (its host mirror is what is uploaded), the block's pending names
+    DevBuf dx_tab, dx_name_off, dx_arena, dx_group, dx_met, dx_pend, dx_pend_list, dx_state, dx_lsamp, dx_out;
+    std::vector<DemuxSlot> dx_tab_host;
+    std::vector<uint2> dx_name_off_host;
+    std::vector<unsigned char> dx_arena_host;
+    std::vector<int64_t> dx_pend_off;     // the pending names of the block scanned last, in order of their first read ...
+    std::vector<int32_t> dx_pend_len;
+    std::vector<char> dx_pend_blob;       // ... and their bytes
+    bool dx_on = false;                   // wk_demux_begin
+    bool dx_looked = false;               // wk_demux_pending has looked the scanned block's samples up
+    bool dx_runs = false;                 // ... and its run starts are told, its subject map and exclusion set applied
+    int dx_status = 1;                    // ... and what it found
+    bool dx_chunk = false;                // the staged chunk is wk_dtok_stage_reads'
+    int32_t dx_groups_n = 0;              // samples that have a group (wk_demux_register)
+    uint64_t dx_hash_mask = 0;            // (tests) option "demux_hash_mask"
+    int64_t dx_max_opt = 0;               // (tests) option "demux_max_samples"
     bool dt_keep_reads = false;   // wk_dtok_keep_reads: wk_dtok_emit places the records in read order and keeps the block
     bool dt_emitted = false;      // the block scanned last was emitted with its reads kept
     uint32_t dt_emit_reads = 0;
@@ -1066,7 +1083,8 @@ void wk_destroy(wk_ctx* c) {
     }
     for (DevBuf* b : {&c->d_tiles, &c->d_tile_off, &c->d_lines, &c->d_lsubj, &c->d_lmeta, &c->d_start, &c->d_first, &c->d_unknown, &c->d_lbeg, &c->d_lend, &c->d_llen, &c->d_lscan, &c->d_gmap,
                       &c->d_state, &c->d_dict, &c->d_dict2, &c->d_names16, &c->d_arena, &c->d_submap, &c->cv_key[0], &c->cv_key[1], &c->cv_end[0], &c->cv_end[1],
-                      &c->cv_reach, &c->cv_hist, &c->cv_tiles, &c->cv_tile_off, &c->cv_state, &c->cv_stage[0], &c->cv_stage[1], &c->cv_stage[2]})
+                      &c->cv_reach, &c->cv_hist, &c->cv_tiles, &c->cv_tile_off, &c->cv_state, &c->cv_stage[0], &c->cv_stage[1], &c->cv_stage[2],
+                      &c->dx_tab, &c->dx_name_off, &c->dx_arena, &c->dx_group, &c->dx_met, &c->dx_pend, &c->dx_pend_list, &c->dx_state, &c->dx_lsamp, &c->dx_out})
         b->release();
     for (wk_ctx::ResidentText& r : c->resident) {
         (void)hipFree(r.dev);
@@ -1126,6 +1144,15 @@ int wk_set_option(wk_ctx* c, const char* name, int64_t value) {
         if (value != 0 && (value < kCoverCapMin || value > kCoverCapMax))
             return fail(c, WK_E_ARG, "cover_cap_rows must be 0 or in [%lld, %lld]", (long long)kCoverCapMin, (long long)kCoverCapMax);
         c->cv_cap_opt = value;
+        return WK_OK;
+    }
+    if (!strcmp(name, "demux_hash_mask")) {  // (tests) AND-ed into every hash of a sample name, 0: none; before wk_demux_begin
+        c->dx_hash_mask = (uint64_t)value;
+        return WK_OK;
+    }
+    if (!strcmp(name, "demux_max_samples")) {  // (tests) samples the table takes, 0: kDemuxMaxSamples; before wk_demux_begin
+        if (value < 0 || value > (int64_t)kDemuxMaxSamples) return fail(c, WK_E_ARG, "demux_max_samples must be in [0, %u]", kDemuxMaxSamples);
+        c->dx_max_opt = value;
         return WK_OK;
     }
     return fail(c, WK_E_ARG, "unknown option '%s' (launch shapes and ablation switches: wk_tune)", name);
@@ -1652,6 +1679,7 @@ int wk_chunk_stage(wk_ctx* c, const int32_t* subj, const int32_t* qoff, int64_t 
     c->subj_is_set = (subj_flags & WK_SUBJ_IS_SET) != 0;
     c->subj_indexed = (subj_flags & WK_SUBJ_INDEXED) != 0;
     c->chunk_valid = true;
+    c->dx_chunk = false;
     return WK_OK;
 }
 
@@ -3343,6 +3371,8 @@ static int dtok_scan_impl(wk_ctx* c, wk_tok* tok, const char* text, int64_t begi
     c->dt_ready = false;
     c->dt_extra = extra != 0;
     c->cv_line_next = 0;
+    c->dx_looked = false;
+    c->dx_runs = false;
     // (an exclusion set: the plain flavour takes it as kLineExcluded entries of the subject map, wk_dtok_subject_map;
     // the "ex" parsers' way with it -- align.py:481-547 yields a stale pool at the end of a file -- stays the host's)
     if (!wkx_tok_device_ok(tok) && (extra || !c->dt_submap_on)) return WK_OK;
@@ -4653,6 +4683,7 @@ static int dtok_stage_impl(wk_ctx* c, const int32_t* genome_of_subject, int32_t 
     c->sb_valid = false;
     c->chunk_valid = false;
     c->acc_open = append;
+    c->dx_chunk = false;
     *n_reads = reads;
     *n_hits = hits;
     *status = 0;
@@ -4662,6 +4693,331 @@ static int dtok_stage_impl(wk_ctx* c, const int32_t* genome_of_subject, int32_t 
 int wk_dtok_stage_hits(wk_ctx* c, const int32_t* genome_of_subject, int32_t n_subjects, double th, int64_t* n_reads,
                        int64_t* n_hits, int* status) {
     return dtok_stage_impl(c, genome_of_subject, n_subjects, th, false, n_reads, n_hits, status);
+}
+
+// ---- demultiplexing on the device (wk_demux.hpp) ---------------------------------------------------------------------
+
+static uint32_t demux_max(const wk_ctx* c) { return c->dx_max_opt ? (uint32_t)c->dx_max_opt : kDemuxMaxSamples; }
+
+static DemuxArgs demux_args(wk_ctx* c) {
+    DemuxArgs d{};
+    d.tab = c->dx_tab.as<DemuxSlot>();
+    d.name_off = c->dx_name_off.as<uint2>();
+    d.arena = c->dx_arena.as<unsigned char>();
+    d.group = c->dx_group.as<int32_t>();
+    d.met = c->dx_met.as<unsigned char>();
+    d.pend = c->dx_pend.as<DemuxPend>();
+    d.pend_list = c->dx_pend_list.as<uint32_t>();
+    d.state = c->dx_state.as<uint32_t>();
+    d.lsamp = c->dx_lsamp.as<int32_t>();
+    d.hash_mask = c->dx_hash_mask;
+    const uint32_t known = (uint32_t)c->dx_name_off_host.size(), most = demux_max(c);
+    d.max_new = most > known ? most - known : 0u;
+    return d;
+}
+
+int wk_demux_begin(wk_ctx* c, int on) {
+    if (!c) return WK_E_ARG;
+    DeviceGuard guard(c->device);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->dx_on = on != 0;
+    c->dx_looked = false;
+    c->dx_chunk = false;
+    c->dx_groups_n = 0;
+    c->dx_name_off_host.clear();
+    c->dx_arena_host.clear();
+    c->dx_tab_host.assign(on ? kDemuxSlots : 0u, DemuxSlot{0ull, 0u, 0u});
+    if (!on) return WK_OK;
+    static_assert(sizeof(DemuxSlot) == 16 && sizeof(DemuxPend) == 16, "16-byte slots");
+    HIP_TRY(c, c->dx_tab.reserve((size_t)kDemuxSlots * sizeof(DemuxSlot)));
+    HIP_TRY(c, c->dx_pend.reserve((size_t)kDemuxSlots * sizeof(DemuxPend)));
+    HIP_TRY(c, c->dx_pend_list.reserve((size_t)kDemuxMaxSamples * 4));
+    HIP_TRY(c, c->dx_met.reserve(kDemuxMaxSamples));
+    HIP_TRY(c, c->dx_name_off.reserve(64));
+    HIP_TRY(c, c->dx_arena.reserve(64));
+    HIP_TRY(c, c->dx_group.reserve(64));
+    HIP_TRY(c, c->dx_state.reserve(64));
+    HIP_TRY(c, hipMemsetAsync(c->dx_tab.p, 0, (size_t)kDemuxSlots * sizeof(DemuxSlot), c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return WK_OK;
+}
+
+// run starts, subject map and exclusion set of the scanned block (as dtok_emit_launch has them), then the lookup of its
+// reads' samples; the pending names end up in dx_pend_*
+static int demux_lookup(wk_ctx* c) {
+    c->dx_pend_off.clear();
+    c->dx_pend_len.clear();
+    c->dx_pend_blob.clear();
+    c->dx_status = 1;
+    const uint32_t lines = c->dt_lines;
+    if (lines == 0) {
+        c->dx_status = 0;
+        c->dx_looked = true;
+        return WK_OK;
+    }
+    DeviceGuard guard(c->device);
+    KtScope kt_scope(c);
+    HIP_TRY(c, c->dx_lsamp.reserve((size_t)lines * 8));
+    HIP_TRY(c, hipMemsetAsync(c->dx_pend.p, 0, (size_t)kDemuxSlots * sizeof(DemuxPend), c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->dx_state.p, 0, 16, c->stream));
+    const DtokArgs a = dtok_args(c);
+    const DemuxArgs d = demux_args(c);
+    const dim3 grid((lines + kDtokThreads - 1) / kDtokThreads);
+    KernelTimer* kt = ktimer_begin(c, "demux_lookup");
+    // (once per scanned block: the runs are told with every mapped line in place -- a run the exclusion set drops still
+    // separates its neighbours)
+    if (!c->dx_runs) {
+        hipLaunchKernelGGL(dtok_runs_kernel, grid, dim3(kDtokThreads), 0, c->stream, a);
+        if (a.submap && !c->dt_mapped) {
+            hipLaunchKernelGGL(dtok_submap_kernel, grid, dim3(kDtokThreads), 0, c->stream, a);
+            if (c->dt_has_excl) {
+                HIP_TRY(c, hipMemsetAsync(c->d_first.p, 0, lines, c->stream));
+                hipLaunchKernelGGL(dtok_excl_mark_kernel, grid, dim3(kDtokThreads), 0, c->stream, a);
+                hipLaunchKernelGGL(dtok_excl_drop_kernel, grid, dim3(kDtokThreads), 0, c->stream, a);
+            }
+            c->dt_mapped = true;
+        }
+        c->dx_runs = true;
+    }
+    hipLaunchKernelGGL(demux_lookup_kernel, grid, dim3(kDtokThreads), 0, c->stream, a, d);
+    hipLaunchKernelGGL(demux_verify_kernel, grid, dim3(kDtokThreads), 0, c->stream, a, d);
+    ktimer_end(c, kt);  // (the launches alone: the waits below are the host's)
+    HIP_TRY(c, hipGetLastError());
+    uint32_t st[4] = {0, 0, 0, 0};
+    DtokState ds{};
+    for (uint32_t round = 0;; ++round) {
+        HIP_TRY(c, small_back(c, 2, c->dx_state.p, 16));
+        if (round == 0) HIP_TRY(c, small_back(c, 0, c->d_state.p, sizeof ds));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        small_back_get(c, 2, st, 16);
+        if (round == 0) small_back_get(c, 0, &ds, sizeof ds);
+        if (st[0] || ds.flags || st[2] == 0u) break;
+        // (names that share a hash with another name: each claims the next slot of its probe, one round per such name)
+        if (round > kDemuxMaxSamples) return fail(c, WK_E_STATE, "the pending sample names do not settle");
+        kt = ktimer_begin(c, "demux_reclaim");  // (the last round's time is the one kept)
+        hipLaunchKernelGGL(store_u32_kernel, dim3(1), dim3(1), 0, c->stream, c->dx_state.as<uint32_t>() + 2, 0u);
+        hipLaunchKernelGGL(demux_reclaim_kernel, grid, dim3(kDtokThreads), 0, c->stream, a, d);
+        hipLaunchKernelGGL(demux_verify_kernel, grid, dim3(kDtokThreads), 0, c->stream, a, d);
+        ktimer_end(c, kt);
+        HIP_TRY(c, hipGetLastError());
+    }
+    c->dx_looked = true;
+    if (st[0] & kDemuxFull) {
+        c->dx_status = 1;
+        return WK_OK;
+    }
+    if (st[0] || ds.flags) {  // (a name the host has not mapped, dtok_submap_kernel: the host tokenizer's block)
+        c->dx_status = 2;
+        return WK_OK;
+    }
+    const uint32_t n = st[1];
+    if (n > d.max_new || n > kDemuxMaxSamples) {
+        c->dx_status = 1;
+        return WK_OK;
+    }
+    c->dx_status = 0;
+    if (n == 0) return WK_OK;
+    HIP_TRY(c, c->dx_out.reserve((size_t)n * sizeof(uint4)));
+    hipLaunchKernelGGL(demux_pending_kernel, dim3((n + kDtokThreads - 1) / kDtokThreads), dim3(kDtokThreads), 0, c->stream, a, d, n,
+                       c->dx_out.as<uint4>());
+    HIP_TRY(c, hipGetLastError());
+    std::vector<uint4> got(n);
+    HIP_TRY(c, hipMemcpyAsync(got.data(), c->dx_out.p, (size_t)n * sizeof(uint4), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    std::sort(got.begin(), got.end(), [](const uint4& x, const uint4& y) { return x.x < y.x; });
+    size_t total = 0;
+    for (const uint4& g : got) {
+        if ((size_t)g.y + g.z > (size_t)c->dt_n) return fail(c, WK_E_STATE, "a pending sample name lies outside the block");
+        c->dx_pend_off.push_back((int64_t)total);
+        c->dx_pend_len.push_back((int32_t)g.z);
+        total += g.z;
+    }
+    c->dx_pend_blob.resize(total);
+    // the names' bytes come back from the device (the host's bytes of a block copied ahead may be gone): one by one
+    // while they are few, with the whole block otherwise
+    if (!c->dt_text) return fail(c, WK_E_STATE, "the scanned block's text has been dropped");
+    if (n > 128u) {
+        std::vector<char> back(c->dt_n);
+        HIP_TRY(c, hipMemcpyAsync(back.data(), c->dt_text, c->dt_n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        for (size_t k = 0; k < got.size(); ++k)
+            if (got[k].z) std::memcpy(c->dx_pend_blob.data() + c->dx_pend_off[k], back.data() + got[k].y, got[k].z);
+    } else {
+        for (size_t k = 0; k < got.size(); ++k)
+            if (got[k].z)
+                HIP_TRY(c, hipMemcpyAsync(c->dx_pend_blob.data() + c->dx_pend_off[k], c->dt_text + got[k].y, got[k].z, hipMemcpyDeviceToHost,
+                                          c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    return WK_OK;
+}
+
+int wk_demux_pending(wk_ctx* c, int64_t* off, int32_t* len, int32_t cap, int32_t* n, char* blob, int64_t blob_cap, int64_t* n_bytes,
+                     int* status) {
+    if (!c || !n || !n_bytes || !status || cap < 0 || blob_cap < 0) return WK_E_ARG;
+    *n = 0;
+    *n_bytes = 0;
+    *status = 1;
+    if (!c->dx_on) return fail(c, WK_E_STATE, "wk_demux_begin has not been called");
+    if (!c->dx_looked) {
+        if (!c->dt_ready || c->dt_extra) return fail(c, WK_E_STATE, "no block scanned for the plain flavour (wk_dtok_scan)");
+        const int rc = demux_lookup(c);
+        if (rc) return rc;
+    }
+    *status = c->dx_status;
+    *n = (int32_t)c->dx_pend_off.size();
+    *n_bytes = (int64_t)c->dx_pend_blob.size();
+    if (!off && !len && !blob) return WK_OK;
+    if (!off || !len || cap < *n || (*n_bytes > 0 && (!blob || blob_cap < *n_bytes))) return fail(c, WK_E_CAPACITY, "pending sample buffers too small");
+    std::copy(c->dx_pend_off.begin(), c->dx_pend_off.end(), off);
+    std::copy(c->dx_pend_len.begin(), c->dx_pend_len.end(), len);
+    if (*n_bytes) std::memcpy(blob, c->dx_pend_blob.data(), (size_t)*n_bytes);
+    return WK_OK;
+}
+
+int wk_demux_register(wk_ctx* c, const char* blob, const int64_t* off, int32_t n, const int32_t* group, int32_t n_total) {
+    if (!c || n < 0 || n_total < 0 || (n > 0 && (!off || !blob)) || (n_total > 0 && !group)) return WK_E_ARG;
+    if (!c->dx_on) return fail(c, WK_E_STATE, "wk_demux_begin has not been called");
+    const size_t known = c->dx_name_off_host.size();
+    if (known + (size_t)n > demux_max(c)) return fail(c, WK_E_CAPACITY, "more than %u samples", demux_max(c));
+    if ((size_t)n_total != known + (size_t)n) return fail(c, WK_E_ARG, "a group for every sample of the table: %zu", known + (size_t)n);
+    for (int32_t i = 0; i < n_total; ++i)
+        if (group[i] < -1 || group[i] >= (1 << WK_KEY_GROUP_BITS)) return fail(c, WK_E_ARG, "group id outside [-1, %d)", 1 << WK_KEY_GROUP_BITS);
+    for (int32_t k = 0; k < n; ++k) {
+        if (off[k] < 0 || off[k + 1] < off[k] || off[k + 1] - off[k] >= (1ll << 28)) return fail(c, WK_E_ARG, "bad name offsets");
+        const unsigned char* p = reinterpret_cast<const unsigned char*>(blob) + off[k];
+        const uint32_t len = (uint32_t)(off[k + 1] - off[k]);
+        const unsigned long long h = demux_hash_of(c->dx_hash_mask, p, len);  // (the kernels' own hash)
+        uint32_t q = demux_home(h);
+        while (c->dx_tab_host[q].hash != 0ull) {
+            if (c->dx_tab_host[q].hash == h) {
+                const uint2 nm = c->dx_name_off_host[c->dx_tab_host[q].id];
+                if (nm.y == len && (len == 0 || !std::memcmp(c->dx_arena_host.data() + nm.x, p, len)))
+                    return fail(c, WK_E_ARG, "sample name %d is in the table already", k);
+            }
+            q = (q + 1u) & (kDemuxSlots - 1u);
+        }
+        c->dx_tab_host[q] = DemuxSlot{h, (uint32_t)c->dx_name_off_host.size(), 0u};
+        c->dx_name_off_host.push_back(make_uint2((uint32_t)c->dx_arena_host.size(), len));
+        c->dx_arena_host.insert(c->dx_arena_host.end(), p, p + len);
+    }
+    DeviceGuard guard(c->device);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // (a kernel may be reading the tables that are there)
+    int rc;
+    if (n > 0) {
+        if ((rc = upload(c, c->dx_tab, c->dx_tab_host.data(), c->dx_tab_host.size() * sizeof(DemuxSlot)))) return rc;
+        if ((rc = upload(c, c->dx_name_off, c->dx_name_off_host.data(), c->dx_name_off_host.size() * sizeof(uint2)))) return rc;
+        if ((rc = upload(c, c->dx_arena, c->dx_arena_host.data(), c->dx_arena_host.size()))) return rc;
+    }
+    if ((rc = upload(c, c->dx_group, group, (size_t)n_total * 4))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->dx_groups_n = n_total;
+    if (n > 0) c->dx_looked = false;  // (the pending names are in the table now)
+    return WK_OK;
+}
+
+int wk_dtok_stage_reads(wk_ctx* c, int64_t* n_reads, int64_t* n_records, int* status) {
+    if (!c || !n_reads || !n_records || !status) return WK_E_ARG;
+    *status = 1;
+    *n_reads = *n_records = 0;
+    if (!c->dx_on) return fail(c, WK_E_STATE, "wk_demux_begin has not been called");
+    if (!c->dt_ready || c->dt_extra) return fail(c, WK_E_STATE, "no block scanned for the plain flavour (wk_dtok_scan)");
+    if (c->dx_groups_n != (int32_t)c->dx_name_off_host.size()) return fail(c, WK_E_STATE, "samples without a group (wk_demux_register)");
+    if (c->acc_open) return fail(c, WK_E_STATE, "staged hits not counted yet (wk_ordinal_count)");
+    DeviceGuard guard(c->device);
+    KtScope kt_scope(c);
+    // (run starts, subject map, exclusion set: wk_demux_pending has done them, or does now)
+    if (!c->dx_looked || c->dx_status != 0 || !c->dx_pend_off.empty()) {
+        if (!c->dx_looked) {
+            const int rc = demux_lookup(c);
+            if (rc) return rc;
+        }
+        if (c->dx_status != 0) {
+            c->dt_ready = false;
+            return WK_OK;
+        }
+        if (!c->dx_pend_off.empty()) return fail(c, WK_E_STATE, "the block brings samples the table does not hold (wk_demux_pending, wk_demux_register)");
+    }
+    c->dt_ready = false;
+    c->dx_looked = false;
+    c->chunk_valid = false;
+    c->dx_chunk = false;
+    const uint32_t lines = c->dt_lines;
+    const size_t n_samples = c->dx_name_off_host.size();
+    if (n_samples) HIP_TRY(c, hipMemsetAsync(c->dx_met.p, 0, n_samples, c->stream));
+    unsigned long long totals = 0;
+    uint32_t st[4] = {0, 0, 0, 0};
+    DtokState ds{};
+    HIP_TRY(c, c->c_subj.reserve((size_t)lines * 4 + 64));
+    HIP_TRY(c, c->c_qoff.reserve(((size_t)lines + 2) * 4));
+    HIP_TRY(c, c->c_group.reserve(((size_t)lines + 1) * 4));
+    if (lines > 0) {
+        DtokArgs a = dtok_args(c);
+        DemuxArgs d = demux_args(c);
+        d.c_subj = c->c_subj.as<int32_t>();
+        d.c_qoff = c->c_qoff.as<int32_t>();
+        d.c_group = c->c_group.as<int32_t>();
+        d.cap = lines;
+        const uint32_t n_tiles = (lines + kDtokThreads - 1) / kDtokThreads;
+        HIP_TRY(c, c->d_tiles.reserve((size_t)n_tiles * 8));
+        HIP_TRY(c, c->d_tile_off.reserve((size_t)n_tiles * 8));
+        HIP_TRY(c, c->d_lscan.reserve(((size_t)lines + 1) * 8));
+        a.line_scan = c->d_lscan.as<unsigned long long>();
+        HIP_TRY(c, hipMemsetAsync(scalar_u64(c, 3), 0, 8, c->stream));
+        HIP_TRY(c, hipMemsetAsync(c->dx_state.p, 0, 16, c->stream));
+        const dim3 grid(n_tiles);
+        KernelTimer* kt = ktimer_begin(c, "demux_stage");
+        hipLaunchKernelGGL(dtok_first_kernel, grid, dim3(kDtokThreads), 0, c->stream, a);
+        hipLaunchKernelGGL(dtok_hits_kernel<false>, grid, dim3(kDtokThreads), 0, c->stream, a, c->d_tiles.as<unsigned long long>());
+        hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_tiles.as<unsigned long long>(),
+                           c->d_tile_off.as<unsigned long long>(), (int64_t)n_tiles, scalar_u64(c, 3));
+        hipLaunchKernelGGL(dtok_scan_lines_kernel, grid, dim3(kDtokThreads), 0, c->stream, a, c->d_tile_off.as<unsigned long long>());
+        hipLaunchKernelGGL(demux_place_reads_kernel, grid, dim3(kDtokThreads), 0, c->stream, a, d);
+        ktimer_end(c, kt);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, small_back(c, 0, c->d_state.p, sizeof ds));
+        HIP_TRY(c, small_back(c, 1, scalar_u64(c, 3), 8));
+        HIP_TRY(c, small_back(c, 2, c->dx_state.p, 16));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        small_back_get(c, 0, &ds, sizeof ds);
+        small_back_get(c, 1, &totals, 8);
+        small_back_get(c, 2, st, 16);
+    }
+    if (ds.flags || st[0]) return WK_OK;  // (a read of more than WK_MAX_K subjects: the host tokenizer's block)
+    const int64_t records = (int64_t)(totals & 0xFFFFFFFFull), reads = (int64_t)(totals >> 32);
+    if (records > (int64_t)lines || reads > records) return fail(c, WK_E_STATE, "the block's reads do not add up");
+    // (the offsets' last entry; the stream orders it in front of whatever reads them)
+    hipLaunchKernelGGL(store_u32_kernel, dim3(1), dim3(1), 0, c->stream, c->c_qoff.as<uint32_t>() + reads, (uint32_t)records);
+    HIP_TRY(c, hipGetLastError());
+    c->rk_valid[0] = c->rk_valid[1] = false;
+    c->stage_serial += 1;
+    c->cur_subj = c->c_subj.as<int32_t>();
+    c->cur_qoff = c->c_qoff.as<int32_t>();
+    c->n_reads = reads;
+    c->n_records = records;
+    c->has_group = true;
+    c->group_base = 0;
+    c->subj_is_set = true;
+    c->subj_indexed = true;
+    c->chunk_valid = true;
+    c->dx_chunk = true;
+    *n_reads = reads;
+    *n_records = records;
+    *status = 0;
+    return WK_OK;
+}
+
+int wk_demux_fetch(wk_ctx* c, int32_t* group, int64_t group_cap, unsigned char* met, int32_t met_cap) {
+    if (!c || group_cap < 0 || met_cap < 0) return WK_E_ARG;
+    if (!c->dx_on) return fail(c, WK_E_STATE, "wk_demux_begin has not been called");
+    if (!c->dx_chunk || !c->chunk_valid) return fail(c, WK_E_STATE, "no chunk staged by wk_dtok_stage_reads");
+    const size_t n_samples = c->dx_name_off_host.size();
+    if ((group && group_cap < c->n_reads) || (met && (size_t)met_cap < n_samples)) return fail(c, WK_E_CAPACITY, "fetch buffers too small");
+    DeviceGuard guard(c->device);
+    if (group && c->n_reads) HIP_TRY(c, hipMemcpyAsync(group, c->c_group.p, (size_t)c->n_reads * 4, hipMemcpyDeviceToHost, c->stream));
+    if (met && n_samples) HIP_TRY(c, hipMemcpyAsync(met, c->dx_met.p, n_samples, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return WK_OK;
 }
 
 static bool ordinal_tally_jobs(const wk_ctx* c, const wk_job* jobs, int32_t n_jobs) {
@@ -4836,6 +5192,7 @@ static int materialise_gene_lists(wk_ctx* c) {
     c->subj_is_set = false;  // several hits of a read may match the same gene
     c->subj_indexed = false; // gene lists carry feature ids
     c->chunk_valid = true;
+    c->dx_chunk = false;
     return WK_OK;
 }
 

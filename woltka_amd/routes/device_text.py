@@ -1,7 +1,9 @@
 """Alignment text tokenised on the device (csrc/wk_dtok.hpp): blocks read
 into pinned memory, scanned, and appended as packed records (`_run_dtok`) or
-staged as coord-match hits (`_run_dhits`); read maps formatted there
-(csrc/wk_readmap.hpp) and the strata map joined there (csrc/wk_strata.hpp).
+staged as coord-match hits (`_run_dhits`) or, demultiplexed there
+(csrc/wk_demux.hpp), as CSR chunks with a group per read (`_run_ddemux`); read
+maps formatted there (csrc/wk_readmap.hpp) and the strata map joined there
+(csrc/wk_strata.hpp).
 Blocks the kernels leave alone go through the host tokenizer (`_host_block`)."""
 import os
 import time
@@ -959,7 +961,7 @@ class DeviceTextRoute:
             try:
                 t0 = time.perf_counter()
                 done = None
-                if self._spec and not ex:
+                if self._spec and not ex and self._ddemux is None:
                     # (the sample's words are open and the block before went
                     # through: scan and emission with one wait)
                     status, n_lines, done = self.ctx.dtok_scan_emit(
@@ -1004,7 +1006,11 @@ class DeviceTextRoute:
                     self.ctx.dtok_subject_map(self._tok_map)
                     self._tok_map_sent = self._tok_map.size
                 if status == 0:
-                    if n_lines:
+                    if n_lines and self._ddemux is not None:
+                        yield None, ('ddemux', (text, fill, first, final,
+                                                hdr_in, hdr, n_lines)), \
+                            None, None, None, None
+                    elif n_lines:
                         yield None, ('dcover' if cover else 'dtok', (
                             text, fill, first, final, hdr_in, hdr, done)), \
                             None, None, None, None
@@ -1014,7 +1020,8 @@ class DeviceTextRoute:
                     yield from self._host_block(text, fill, first, final,
                                                 hdr_in,
                                                 names=self._dmaps is not None,
-                                                cover=cover)
+                                                cover=cover,
+                                                samples=self._ddemux is not None)
             finally:
                 # (a block in a ring buffer: the reader took the buffer back
                 # when its copy was through)
@@ -1034,7 +1041,8 @@ class DeviceTextRoute:
             # (plain SAM records for the weighted histogram go through the
             # one-kernel tokenizer: no newline count behind a block's copy)
             self.ctx.set_option('dtok_count_ahead', int(bool(
-                ex or self._dmaps is not None or self._dfmt != 'sam')))
+                ex or self._dmaps is not None or self._dfmt != 'sam' or
+                self._ddemux is not None)))
         ahead, whole = taken, None
         if ahead is None:
             whole = open_mapped() if source is None else None
@@ -1101,6 +1109,7 @@ class DeviceTextRoute:
                     break
                 slot = item[0]
                 if may_lag and self._spec and self._dmaps is None and \
+                        self._ddemux is None and \
                         isinstance(slot, tuple) and slot[0] == 'det':
                     t0 = time.perf_counter()
                     begun = self.ctx.dtok_scan_emit_begin(tok, item[1],
@@ -1205,11 +1214,13 @@ class DeviceTextRoute:
                         len(fresh))])
 
     def _host_block(self, buf, fill, first, final, hdr_in, ordinal=False,
-                    names=False, groups=False, cover=False):
+                    names=False, groups=False, cover=False, samples=False):
         """One block of the device route through the host tokenizer after
         all (the general arrays; ``names``: with the descriptors of the query
         names, for the read maps; ``cover``: the "ex" parsers' records with
-        their ranges (coverage subject id, beg, end) as the last item)."""
+        their ranges (coverage subject id, beg, end) as the last item;
+        ``samples``: with the reads' sample ids, numbered like
+        `_tok_samples`, as the fifth item)."""
         ROUTES['host_block'] += 1
         if isinstance(buf, _BlockText):     # (the bytes come back from the device)
             buf = buf.get()
@@ -1242,7 +1253,9 @@ class DeviceTextRoute:
             return
         res = tok.parse(memoryview(buf).cast('B')[:fill], first=first,
                         final=final, fmt=self._dfmt, want_names=names,
-                        extra=3 if cover else False)
+                        extra=3 if cover else False, want_samples=samples)
+        if samples:
+            self._tok_samples.extend(tok.new_samples())
         fresh = tok.new_subjects()
         if fresh:
             self._map_fresh(fresh)
@@ -1252,7 +1265,8 @@ class DeviceTextRoute:
             subj = res['subj'] if self._tok_identity \
                 else self._tok_map[res['subj']]
             yield None, (subj, res['off']), None, \
-                ((buf[:fill], res['qname']) if names else None), None, \
+                ((buf[:fill], res['qname']) if names else None), \
+                (res['sample'] if samples else None), \
                 ((self._tok_cover[res['subj']], res['beg'], res['end'])
                  if cover else None)
 
@@ -1427,6 +1441,79 @@ class DeviceTextRoute:
             n += self.run_chunk(data, None, None, sample, None, None, None,
                                 None, None, False, packed=(subj, qoff),
                                 packed_is_set=not (self._dtrimsub or cover))
+        self.tok.set_header_state(hdr)
+        return n
+
+    def _device_sample_groups(self, allow):
+        """The (sample, no stratum) group of every sample of the device's
+        table (-1: outside the whitelist) -- again after every fold of the
+        count table (the groups are numbered anew)."""
+        names = self._dx_names
+        gid, groups = self.group_ids, self.groups
+        out = np.empty(len(names), dtype=np.int32)
+        for i, name in enumerate(names):
+            if allow is not None and name not in allow:
+                out[i] = -1
+                continue
+            k = (name, None)
+            g = gid.get(k)
+            if g is None:
+                g = len(groups)
+                if g >= MAX_GROUPS:
+                    raise ValueError('Too many (sample, stratum) groups in '
+                                     'one pass.')
+                gid[k] = g
+                groups.append(k)
+            out[i] = g
+        return out
+
+    def _run_ddemux(self, data, packed, sample):
+        """A block the device has scanned under `--demux`: the samples its
+        reads bring are registered (`wk_demux_pending` / `_register`), the
+        block is staged as a CSR chunk with a group per read
+        (`wk_dtok_stage_reads`) and counted by the general evaluator.  A block
+        the kernels refuse -- more samples than the table holds, a read of
+        more subjects than a count key can say -- goes through the host
+        tokenizer with the samples told there."""
+        buf, fill, first, final, hdr_in, hdr, n_lines = packed[1]
+        allow, = self._ddemux
+        self._sync_subjects(data)
+        status, fresh = (1, []) if self._dx_full else self.ctx.demux_pending()
+        if status == 0:
+            names = self._dx_names
+            if fresh:
+                names.extend(x.decode() for x in fresh)
+            # room for the groups and the count keys the block can add (before
+            # its groups are taken: a fold numbers them anew)
+            if len(self.groups) + len(names) + 1 >= MAX_GROUPS // 2:
+                self.collect(data)
+            self._ensure_table(data, n_lines, min(n_lines, len(names) + 1))
+            key = (self._epoch, len(names))
+            if fresh or self._dx_key != key:
+                self.ctx.demux_register(fresh,
+                                        self._device_sample_groups(allow))
+                self._dx_key = key
+            status, n_reads, _ = self.ctx.dtok_stage_reads()
+        elif status & 1:
+            self._dx_full = True    # (the rest of the file: the host's)
+        if status == 0:
+            ROUTES['ddemux'] += 1
+            if n_reads:
+                self._classify_staged(data, False)
+                met, _ = self.ctx.demux_fetch(len(self._dx_names))
+                for i in np.flatnonzero(met).tolist():
+                    s = self._dx_names[i]
+                    for rank in self.ranks:
+                        data[rank].setdefault(s, {})
+            self._n_reads += n_reads
+            return n_reads
+        n = 0
+        for _, (subj, qoff), _, _, ids, _ in self._host_block(
+                buf, fill, first, final, hdr_in, samples=True):
+            n += self.run_chunk(data, None, None, None, None, None, None,
+                                None, None, False, packed=(subj, qoff),
+                                sample_ids=ids, allow=allow,
+                                packed_is_set=not self._dtrimsub)
         self.tok.set_header_state(hdr)
         return n
 

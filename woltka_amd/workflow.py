@@ -24,7 +24,8 @@ import click
 import numpy as np
 
 from .align import NATIVE_FORMATS, infer_align_format, plain_mapper
-from .classify import Engine, cover_on_device, exact_to_numbers
+from .classify import (Engine, cover_on_device, demux_on_device,
+                       exact_to_numbers)
 from .file import (FilesAhead, id2file_from_dir, id2file_from_map, openzip, path2stem,
                    read_ids, read_map_1st, read_map_uniq, readzip, readzip_bytes,
                    stem2rank, write_readmap)
@@ -502,7 +503,13 @@ def classify(
                             cover=cover, fmt=fmt_, part=part, words=words,
                             words_dev=words_dev, dmaps=dmaps,
                             keep_empty=bool(ordinal and rank2dir is not None),
-                            dcover=dcover)
+                            dcover=dcover,
+                            # the samples told on the device too
+                            # (csrc/wk_demux.hpp)
+                            ddemux=(allow,) if demux_on_device(
+                                native_demux, fmt_, coords=bool(ordinal),
+                                sizes=bool(sizes), n_jobs=len(engine.jobs),
+                                replay=engine._replay is not None) else None)
                         if ordinal and rank2dir is not None:
                             chunks = engine.regroup_hits(chunks, n)
                     else:
@@ -530,7 +537,10 @@ def classify(
                         else:
                             qryque, subque = chunk_
                         # sample of every read (demultiplexing / whitelist)
-                        if demux and sample_ids is not None:
+                        if demux and (sample_ids is not None or
+                                      qryque is None):
+                            # (told by the tokenizer -- or on the device,
+                            # `_run_ddemux`: the chunk is a block there)
                             sample_of, reads = None, None
                         elif demux:
                             sample_of, reads = demux_labels(qryque, samples)
