@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define WK_ABI_VERSION 3
+#define WK_ABI_VERSION 4
 
 /* error codes */
 #define WK_OK 0
@@ -805,6 +805,48 @@ uint32_t wk_crc32(uint32_t crc, const char* data, int64_t n);
 int64_t wk_gz_inflate_members(const char* blob, const int64_t* lo,
                               const int64_t* hi, int64_t n, char* out,
                               const int64_t* off, int n_threads);
+
+/* ---- gzip members inflated on the device (csrc/wk_dinflate.hpp) ------------ */
+/* Members that state their size (BGZF 'BC', this library's 'WK') are independent
+ * DEFLATE streams: one wave of the GPU inflates one.  blob[0, n_blob) holds the
+ * members; member i's stream begins at lo[i] (behind its header) and the member
+ * ends at hi[i] (the eight bytes before are its CRC-32 and ISIZE); its text goes
+ * to out[off[i], off[i+1]) (off = running sum of ISIZE, off[0] = 0).
+ * wk_inflate_members_device copies the bytes in, inflates all members in one
+ * launch and copies text and status words out: status[i] = 0, or why member i
+ * failed (1 block type, 2 code lengths, 3 invalid symbol, 4 distance too far
+ * back, 5 more output than stated, 6 input ends inside the stream, 7 stored
+ * LEN / NLEN, 8 size, 9 CRC-32 -- verified on the device); the text of a failed
+ * member is undefined, that of its neighbours is not touched.  The text lies
+ * between guard bytes on the device: WK_E_STATE if one of them changed. */
+int wk_inflate_members_device(wk_ctx* ctx, const char* blob, int64_t n_blob,
+                              const int64_t* lo, const int64_t* hi,
+                              const int64_t* off, int64_t n, char* out,
+                              uint32_t* status);
+
+/* The sibling of wk_dtok_copy_ahead for such members: the next text buffer on
+ * the device is filled with carry[0, n_carry) (a small host copy: the lines the
+ * block before left unfinished) followed by the text of the n_members members
+ * in comp[0, n_comp) (pinned; lo / hi / off as above), inflated there on the
+ * copy stream while the block before is scanned.  [0, stop) of that buffer is
+ * the block (begin must be 0; last_byte = its last byte), and the next
+ * wk_dtok_scan / wk_dtok_scan_emit* called with (comp, 0, stop) scans it;
+ * wk_dtok_text_back hands its text to the host as for any block copied ahead.
+ * wk_dtok_copy_wait(*ticket): comp may be overwritten; WK_E_STATE with a
+ * message that begins "gzip member" if a member of the block failed.
+ * wk_gz_walk_members reads the headers of a whole file[0, n): the members that
+ * hold text -- where each begins (start), where its DEFLATE stream begins (lo),
+ * where it ends (hi), its ISIZE -- into arrays of `cap` entries, empty members
+ * left out.  Returns their number (call with cap = 0 to learn it), or -1 if a
+ * member does not state its size or the chain does not end with the file. */
+int wk_dtok_inflate_ahead(wk_ctx* ctx, const char* comp, int64_t n_comp,
+                          const int64_t* lo, const int64_t* hi,
+                          const int64_t* off, int64_t n_members,
+                          const char* carry, int64_t n_carry, int64_t begin,
+                          int64_t stop, int last_byte, int32_t* ticket);
+int64_t wk_gz_walk_members(const char* file, int64_t n, int64_t* start,
+                           int64_t* lo, int64_t* hi, int64_t* isize,
+                           int64_t cap);
 
 /* ---- gzip input, inflated natively (host; csrc/wk_inflate.cpp) ------------ */
 /* file.readzip's decompressor (woltka/file.py:62-129: `gzip -cdfq` as a child,

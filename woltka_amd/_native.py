@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get('WOLTKA_HIP_LIB') or os.path.join(
     _HERE, 'libwoltka_hip.so')
 
 # constants mirrored from include/woltka_hip.h
-ABI_VERSION = 3
+ABI_VERSION = 4
 OK, E_HIP, E_ARG, E_STATE, E_CAPACITY, E_RANGE, E_TABLE_FULL = (
     0, -1, -2, -3, -4, -5, -6)
 KEY_FEATURE_BITS, KEY_GROUP_BITS, KEY_K_BITS, KEY_JOB_BITS = 28, 21, 12, 3
@@ -77,6 +77,8 @@ SYMBOLS = (
     'wk_coords_parse', 'wk_coords_error', 'wk_coords_sizes',
     'wk_coords_fetch', 'wk_coords_free',
     'wk_gz_bound', 'wk_gz_member', 'wk_crc32', 'wk_gz_inflate_members',
+    'wk_inflate_members_device', 'wk_dtok_inflate_ahead',
+    'wk_gz_walk_members',
     'wk_gunzip_open', 'wk_gunzip_read', 'wk_gunzip_error', 'wk_gunzip_close',
     'wk_text_upload', 'wk_text_clear', 'wk_h2d_rate',
     'wk_dtok_fused_counts', 'wk_ordinal_chunk_counts')
@@ -208,6 +210,17 @@ def load_library():
         'wk_dtok_copy_ahead': (C.c_int, [p, C.c_void_p, C.c_int64, C.c_int64,
                                          C.POINTER(C.c_int32)]),
         'wk_dtok_copy_wait': (C.c_int, [p, C.c_int32]),
+        'wk_dtok_inflate_ahead': (C.c_int, [
+            p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),
+            C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64, C.c_char_p,
+            C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int32)]),
+        'wk_gz_walk_members': (C.c_int64, [
+            C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+            C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64]),
+        'wk_inflate_members_device': (C.c_int, [
+            p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),
+            C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64, C.c_void_p,
+            C.POINTER(C.c_uint32)]),
         'wk_dtok_copy_drop': (C.c_int, [p]),
         'wk_dtok_subject_map': (C.c_int, [p, i32p, C.c_int32]),
         'wk_dtok_ahead_room': (C.c_int, [p, C.POINTER(C.c_int32)]),
@@ -671,7 +684,47 @@ class Context:
         return ticket.value
 
     def dtok_copy_wait(self, ticket):
-        self._check(self._lib.wk_dtok_copy_wait(self._h, int(ticket)))
+        rc = self._lib.wk_dtok_copy_wait(self._h, int(ticket))
+        if rc == E_STATE:
+            msg = self._lib.wk_last_error(self._h).decode()
+            if msg.startswith('gzip member'):   # (a block inflated on the device)
+                raise OSError(msg)
+        self._check(rc)
+
+    def dtok_inflate_ahead(self, comp, n_comp, lo, hi, off, carry, stop, last):
+        """``dtok_copy_ahead`` for a block of gzip members inflated on the
+        device: ``comp[:n_comp]`` (pinned) holds the members (``lo``, ``hi``,
+        ``off`` as for ``inflate_members_device``); the block is ``carry`` +
+        their text, cut at ``stop``; ``last``: its last byte.  The scan is
+        called with ``(comp, 0, stop)``.  Returns the ticket."""
+        raw = np.frombuffer(memoryview(comp), dtype=np.uint8)
+        lo, hi, off = (_arr(x, np.int64) for x in (lo, hi, off))
+        ticket = C.c_int32(-1)
+        self._check(self._lib.wk_dtok_inflate_ahead(
+            self._h, C.c_void_p(raw.ctypes.data), int(n_comp),
+            _ptr(lo, C.c_int64), _ptr(hi, C.c_int64), _ptr(off, C.c_int64),
+            lo.size, bytes(carry), len(carry), 0, int(stop), int(last),
+            C.byref(ticket)))
+        return ticket.value
+
+    def inflate_members_device(self, blob, lo, hi, off):
+        """Inflate gzip members on the device, all in one launch: member i's
+        DEFLATE stream begins at ``blob[lo[i]]``, the member ends at
+        ``hi[i]``, its text goes to ``[off[i], off[i + 1])``.  Returns (text,
+        status): uint8[off[-1]] and per member 0 or why it failed
+        (``wk_inflate_members_device``)."""
+        raw = np.frombuffer(memoryview(blob), dtype=np.uint8)
+        lo, hi, off = (_arr(x, np.int64) for x in (lo, hi, off))
+        if off.size != lo.size + 1 or hi.size != lo.size:
+            raise ValueError('lo, hi of n members and off of n + 1')
+        out = np.empty(int(off[-1]) if off.size else 0, dtype=np.uint8)
+        status = np.zeros(lo.size, dtype=np.uint32)
+        self._check(self._lib.wk_inflate_members_device(
+            self._h, C.c_void_p(raw.ctypes.data if raw.size else 0), raw.size,
+            _ptr(lo, C.c_int64), _ptr(hi, C.c_int64), _ptr(off, C.c_int64),
+            lo.size, C.c_void_p(out.ctypes.data if out.size else 0),
+            _ptr(status, C.c_uint32)))
+        return out, status
 
     def dtok_copy_drop(self):
         """Forget the blocks copied ahead that no scan has asked for."""
@@ -1560,6 +1613,49 @@ def gz_inflate_members(blob, spans, out=None, n_threads=0):
         raise OSError(f'gzip member {-rc - 1} does not inflate to what its '
                       'trailer says')
     return out[:total], inside
+
+
+def gz_walk_members(blob):
+    """(start, lo, hi, isize) -- int64 arrays -- of the members of a gzip
+    file that is a chain of members stating their size (BGZF, 'WK'), empty
+    members left out; None for any other file (``wk_gz_walk_members``)."""
+    lib = load_library()
+    raw = np.frombuffer(memoryview(blob), dtype=np.uint8)
+    if not raw.size:
+        return None
+    addr = C.c_void_p(raw.ctypes.data)
+    n = lib.wk_gz_walk_members(addr, raw.size, None, None, None, None, 0)
+    if n < 0:
+        return None
+    out = [np.zeros(max(n, 1), dtype=np.int64) for _ in range(4)]
+    if lib.wk_gz_walk_members(addr, raw.size,
+                              *(_ptr(x, C.c_int64) for x in out), n) != n:
+        return None
+    return tuple(x[:n] for x in out)
+
+
+def gz_inflate_streams(blob, lo, hi, isize, n_threads=1):
+    """The text of members given by their DEFLATE streams' starts ``lo`` and
+    the members' ends ``hi`` (``gz_walk_members``), inflated on the host;
+    OSError if one does not inflate to what its trailer says."""
+    lib = load_library()
+    raw = np.frombuffer(memoryview(blob), dtype=np.uint8)
+    # (wk_gz_inflate_members takes members with the 20-byte header wk_gz_member writes)
+    lo = _arr(np.asarray(lo, dtype=np.int64) - 20, np.int64)
+    hi = _arr(hi, np.int64)
+    off = np.zeros(lo.size + 1, dtype=np.int64)
+    np.cumsum(np.asarray(isize, dtype=np.int64), out=off[1:])
+    out = np.empty(int(off[-1]), dtype=np.uint8)
+    if lo.size:
+        rc = lib.wk_gz_inflate_members(
+            C.c_void_p(raw.ctypes.data), _ptr(lo, C.c_int64),
+            _ptr(hi, C.c_int64), lo.size,
+            C.c_void_p(out.ctypes.data if out.size else 0),
+            _ptr(off, C.c_int64), int(n_threads))
+        if rc != 0:
+            raise OSError('a gzip member does not inflate to what its '
+                          'trailer says (stream, size, CRC-32)')
+    return out
 
 
 def crc32(data, crc=0):

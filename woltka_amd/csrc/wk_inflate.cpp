@@ -675,6 +675,7 @@ struct Gunzip {
     uint64_t len_run = 0;
     bool chain = false;  // members that state their size
     size_t chain_at = 0;
+    size_t start_at = 0;  // where the producer's first member begins (a chain that goes on as one stream)
     size_t chunk_bytes = 1 << 20;
 
     ~Gunzip() {
@@ -869,9 +870,9 @@ void produce(Gunzip* g) {
         g->cv.notify_all();
     };
     MemberHead mh;
-    const int hr = parse_member_head(file, n, mh);
+    const int hr = parse_member_head(file + g->start_at, n - g->start_at, mh);
     if (hr != 0) return fail(hr == 1 ? "not a gzip file" : "the gzip header is cut short");
-    int64_t pos = (int64_t)mh.size * 8;
+    int64_t pos = (int64_t)(g->start_at + mh.size) * 8;
     // (two threads decode less than one: every chunk but a wave's first is decoded into cells and
     // resolved, about twice the work per byte)
     const int T = g->threads < 3 ? 1 : g->threads;
@@ -979,6 +980,33 @@ struct wk_gunzip {
 
 extern "C" {
 
+// The members of a chain that state their size, from their headers alone (wk_dinflate.hpp inflates them).
+int64_t wk_gz_walk_members(const char* file, int64_t n, int64_t* start, int64_t* lo, int64_t* hi, int64_t* isize, int64_t cap) {
+    if (!file || n <= 0 || cap < 0 || (cap && (!start || !lo || !hi || !isize))) return -1;
+    const uint8_t* p = reinterpret_cast<const uint8_t*>(file);
+    int64_t at = 0, count = 0;
+    while (at < n) {
+        MemberHead mh;
+        if (parse_member_head(p + at, (size_t)(n - at), mh) != 0 || mh.stated < 0) return -1;
+        if (mh.stated < (int64_t)mh.size + 8 || mh.stated > n - at) return -1;
+        const int64_t end = at + mh.stated;
+        uint32_t crc, sz;
+        std::memcpy(&crc, p + end - 8, 4);
+        std::memcpy(&sz, p + end - 4, 4);
+        if (sz != 0 || crc != 0) {   // (BGZF's EOF block, `cat a b`: a member without text is left out)
+            if (count < cap) {
+                start[count] = at;
+                lo[count] = at + (int64_t)mh.size;
+                hi[count] = end;
+                isize[count] = (int64_t)sz;
+            }
+            ++count;
+        }
+        at = end;
+    }
+    return count;
+}
+
 // Open `path` (a regular gzip file) for inflating on up to `n_threads` threads.  NULL on failure
 // (`err`, if given, says why): not a regular file, not gzip.  (file.readzip, woltka/file.py:62-129.)
 wk_gunzip* wk_gunzip_open(const char* path, int n_threads, char* err, size_t err_cap) {
@@ -1057,8 +1085,12 @@ int64_t wk_gunzip_read(wk_gunzip* h, char* dst_c, int64_t cap) {
             if (hr == 2 || mh.stated < (int64_t)mh.size + 8 || at + (size_t)mh.stated > g.size) {
                 if (fill == 0) {  // (nothing to hand out but empty members: 0 bytes would read as the end of the data)
                     if (hr == 0 && mh.stated < 0) {
-                        g.err = "a gzip member without a stated size inside a chain of members that state theirs";
-                        return -1;
+                        // a member that does not state its size behind members that do (`cat a.bgzf b.gz`): from
+                        // here on the file is read as one stream, whatever its later members state
+                        g.chain = false;
+                        g.start_at = at;
+                        g.producer = std::thread(produce, &g);
+                        return wk_gunzip_read(h, dst_c, cap);
                     }
                     g.err = "a gzip member is cut short";
                     return -1;

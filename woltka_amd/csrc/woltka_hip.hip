@@ -33,6 +33,7 @@
 #include "wk_weigh.hpp"
 #include "wk_sized.hpp"
 #include "wk_logred.hpp"
+#include "wk_dinflate.hpp"
 
 using namespace wk;
 
@@ -357,6 +358,16 @@ struct wk_ctx {
         unsigned long long n_newlines;
     };
     std::vector<ResidentText> resident;
+    // gzip members inflated on the device (wk_dinflate.hpp): the compressed bytes, the members' spans, the text and
+    // the status words of wk_inflate_members_device
+    DevBuf di_blob, di_meta, di_out, di_status;
+    // ... and of the blocks wk_dtok_inflate_ahead fills, one set per text buffer in use; the kernel's "a member failed"
+    // word of each lands in pinned memory behind the kernel (read by wk_dtok_copy_wait)
+    DevBuf di_comp_k[kTextBufs], di_meta_k[kTextBufs], di_status_k[kTextBufs];
+    uint32_t* di_any_host = nullptr;   // [kTextBufs] pinned
+    bool di_used[kTextBufs] = {};
+    std::vector<int64_t> di_meta_host[kTextBufs];   // what the copies of a block's spans and carry read until they are through
+    std::vector<char> di_carry_host[kTextBufs];
     const unsigned char* dt_text = nullptr;  // the text of the block scanned last
     int dt_fmt = 0;   // WK_FMT_* of the blocks (wk_dtok_format)
     uint32_t dt_n = 0, dt_lines = 0, dt_dict_mask = 0;
@@ -1070,6 +1081,7 @@ void wk_destroy(wk_ctx* c) {
     for (wk_ctx::StreamTables& T : c->st)
         for (DevBuf* b : {&T.dsparse, &T.dparent, &T.dself, &T.rnode, &T.subj_node, &T.subj_rank}) b->release();
     c->c_words.release();
+    for (DevBuf* b : {&c->di_blob, &c->di_meta, &c->di_out, &c->di_status}) b->release();
     for (DevBuf& b : c->w_stream) b.release();
     c->w_backup2.release();
     c->w_backup3.release();
@@ -1078,6 +1090,9 @@ void wk_destroy(wk_ctx* c) {
     for (int q = 0; q < wk_ctx::kTextBufs; ++q) {
         c->d_tiles_k[q].release();
         c->d_tile_off_k[q].release();
+        c->di_comp_k[q].release();
+        c->di_meta_k[q].release();
+        c->di_status_k[q].release();
         c->d_textbuf[q].release();
         if (q % wk_ctx::kSlabBufs == 0) c->d_textslab[q / wk_ctx::kSlabBufs].release();
     }
@@ -1101,6 +1116,7 @@ void wk_destroy(wk_ctx* c) {
         if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : c->copy_evm)
         if (ev) (void)hipEventDestroy(ev);
+    if (c->di_any_host) (void)hipHostFree(c->di_any_host);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->count_stream) (void)hipStreamDestroy(c->count_stream);
     if (c->res_ev) (void)hipEventDestroy(c->res_ev);
@@ -3034,7 +3050,22 @@ int wk_host_unregister(wk_ctx* c, const void* p) {
     return WK_OK;
 }
 
-static int dtok_copy_impl(wk_ctx* c, const char* text, int64_t begin, int64_t stop, bool detached, int32_t* ticket) {
+static int dinf_check_spans(wk_ctx* c, int64_t n_blob, const int64_t* lo, const int64_t* hi, const int64_t* off, int64_t n);
+static void dinf_launch(wk_ctx* c, const unsigned char* d_blob, const int64_t* d_meta, int64_t n, unsigned char* d_out, uint32_t* d_status,
+                        hipStream_t s);
+
+// (wk_dtok_inflate_ahead) what a block is made of when its text is inflated on the device instead of copied
+struct DinfAhead {
+    int64_t n_comp;
+    const int64_t *lo, *hi, *off;
+    int64_t n_members;
+    const char* carry;
+    int64_t n_carry;
+    char last;
+};
+
+static int dtok_copy_impl(wk_ctx* c, const char* text, int64_t begin, int64_t stop, bool detached, int32_t* ticket,
+                          const DinfAhead* inf = nullptr) {
     if (!c || !text || begin < 0 || stop < begin) return WK_E_ARG;
     if (ticket) *ticket = -1;
     Lap lap(&c->lap_s[0]);
@@ -3070,12 +3101,40 @@ static int dtok_copy_impl(wk_ctx* c, const char* text, int64_t begin, int64_t st
     // (at least a full block's worth from the start: a file's first blocks are small, and growing a buffer
     // three times means three hipFree / hipMalloc pairs per buffer while the dictionary is cold)
     lap_mark(0);
-    HIP_TRY(c, text_buffer(c, k, (size_t)n + 64));
+    HIP_TRY(c, text_buffer(c, k, (inf ? (size_t)(inf->n_carry + inf->off[inf->n_members]) : (size_t)n) + 64));
     lap_mark(1);
     HIP_TRY(c, hipEventRecord(c->copy_ev0[k], c->copy_stream));
-    // (only the copy on this stream: the 64 zero bytes behind the text are a fill
-    // kernel, which wk_dtok_scan launches on its own stream behind the copy's event)
-    HIP_TRY(c, copy_text_async(c, c->d_textptr[k], text + begin, (size_t)n, c->copy_stream));
+    c->di_used[k] = inf != nullptr;
+    if (inf) {
+        // the carry, then the members' text behind it: compressed bytes and spans in, one launch of the inflate
+        // kernel, its failure word out to pinned memory -- all on the copy stream, so the scan of the block before
+        // goes on meanwhile.  (Spans and carry are the caller's for this call only: the copies read this buffer's own.)
+        const int64_t nm = inf->n_members;
+        if (!c->di_any_host) HIP_TRY(c, hipHostMalloc((void**)&c->di_any_host, sizeof(uint32_t) * wk_ctx::kTextBufs, hipHostMallocDefault));
+        HIP_TRY(c, c->di_comp_k[k].reserve((size_t)inf->n_comp));
+        HIP_TRY(c, c->di_meta_k[k].reserve((size_t)(3 * nm + 1) * 8));
+        HIP_TRY(c, c->di_status_k[k].reserve((size_t)(nm + 2) * 4));
+        std::vector<int64_t>& meta = c->di_meta_host[k];
+        meta.resize((size_t)(3 * nm + 1));
+        std::copy(inf->lo, inf->lo + nm, meta.begin());
+        std::copy(inf->hi, inf->hi + nm, meta.begin() + nm);
+        for (int64_t i = 0; i <= nm; ++i) meta[(size_t)(2 * nm + i)] = inf->off[i] + inf->n_carry;
+        c->di_carry_host[k].assign(inf->carry, inf->carry + inf->n_carry);
+        int64_t* d_meta = c->di_meta_k[k].as<int64_t>();
+        c->di_any_host[k] = 0;
+        if (inf->n_carry)
+            HIP_TRY(c, hipMemcpyAsync(c->d_textptr[k], c->di_carry_host[k].data(), (size_t)inf->n_carry, hipMemcpyHostToDevice, c->copy_stream));
+        HIP_TRY(c, hipMemcpyAsync(c->di_comp_k[k].p, text, (size_t)inf->n_comp, hipMemcpyHostToDevice, c->copy_stream));
+        HIP_TRY(c, hipMemcpyAsync(d_meta, meta.data(), meta.size() * 8, hipMemcpyHostToDevice, c->copy_stream));
+        HIP_TRY(c, hipMemsetAsync(c->di_status_k[k].p, 0, (size_t)(nm + 2) * 4, c->copy_stream));
+        dinf_launch(c, c->di_comp_k[k].as<unsigned char>(), d_meta, nm, c->d_textptr[k], c->di_status_k[k].as<uint32_t>(), c->copy_stream);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(&c->di_any_host[k], c->di_status_k[k].as<uint32_t>() + nm, 4, hipMemcpyDeviceToHost, c->copy_stream));
+    } else {
+        // (only the copy on this stream: the 64 zero bytes behind the text are a fill
+        // kernel, which wk_dtok_scan launches on its own stream behind the copy's event)
+        HIP_TRY(c, copy_text_async(c, c->d_textptr[k], text + begin, (size_t)n, c->copy_stream));
+    }
     HIP_TRY(c, hipEventRecord(c->copy_evm[k], c->copy_stream));
     lap_mark(2);
     // ... and, behind the copy, the count of the block's newlines -- on a stream of its own, so that the next
@@ -3099,7 +3158,7 @@ static int dtok_copy_impl(wk_ctx* c, const char* text, int64_t begin, int64_t st
     {
         std::lock_guard<std::mutex> lock(c->copy_mu);
         c->copy_n[k] = n;
-        c->copy_last[k] = text[stop - 1];
+        c->copy_last[k] = inf ? inf->last : text[stop - 1];
         c->copy_detached[k] = detached;
         c->copy_src[k] = text + begin;
     }
@@ -3127,7 +3186,25 @@ int wk_dtok_copy_wait(wk_ctx* c, int32_t ticket) {
     if (ticket >= wk_ctx::kTextBufs || !c->copy_evm[ticket]) return fail(c, WK_E_ARG, "not a ticket of wk_dtok_copy_ahead");
     DeviceGuard guard(c->device);
     HIP_TRY(c, hipEventSynchronize(c->copy_evm[ticket]));
+    if (c->di_used[ticket] && c->di_any_host && c->di_any_host[ticket])
+        return fail(c, WK_E_STATE, "gzip member: one of the block does not inflate to what its trailer says (stream, size, CRC-32)");
     return WK_OK;
+}
+
+// The sibling of wk_dtok_copy_ahead for gzip members that state their size: the next text buffer is filled with
+// carry[0, n_carry) followed by the text of the members, inflated there (wk_dinflate.hpp), and [0, stop) of it is the
+// block that the scan tagged (comp, 0, stop) finds.  What lies behind `stop` in the buffer is not part of the block.
+int wk_dtok_inflate_ahead(wk_ctx* c, const char* comp, int64_t n_comp, const int64_t* lo, const int64_t* hi, const int64_t* off,
+                          int64_t n_members, const char* carry, int64_t n_carry, int64_t begin, int64_t stop, int last_byte,
+                          int32_t* ticket) {
+    if (!c || !comp || n_comp <= 0 || !lo || !hi || !off || n_members <= 0 || n_members >= (1ll << 31) || n_carry < 0 || (n_carry && !carry) ||
+        !ticket)
+        return WK_E_ARG;
+    if (begin != 0) return fail(c, WK_E_ARG, "a block inflated on the device begins with its buffer (begin = %lld)", (long long)begin);
+    if (int rc = dinf_check_spans(c, n_comp, lo, hi, off, n_members)) return rc;
+    if (stop <= 0 || stop > n_carry + off[n_members]) return fail(c, WK_E_ARG, "the block ends outside its text");
+    const DinfAhead inf{n_comp, lo, hi, off, n_members, carry, n_carry, (char)last_byte};
+    return dtok_copy_impl(c, comp, 0, stop, true, ticket, &inf);
 }
 
 // The text blocks scanned from now on belong to `text_bytes` bytes of one sample (0: unknown again): the buffers of its
@@ -3151,6 +3228,12 @@ int wk_dtok_copy_drop(wk_ctx* c) {
             c->buf_state[q] = wk_ctx::kBufFree;
             c->copy_src[q] = nullptr;
             c->copy_counted[q] = false;
+        }
+    for (int q = 0; q < wk_ctx::kTextBufs; ++q)
+        if (c->buf_state[q] == wk_ctx::kBufFree) {   // (compressed bytes of blocks long scanned)
+            c->di_comp_k[q].release();
+            c->di_meta_k[q].release();
+            c->di_status_k[q].release();
         }
     // (the slabs a reader far ahead of the scans took -- up to 12 GB -- go back to the device once none of their
     // buffers is in use: what follows the file, count tables and records, must not compete with parked text.
@@ -3199,6 +3282,66 @@ int wk_dtok_text_back(wk_ctx* c, char* out, int64_t n) {
     DeviceGuard guard(c->device);
     HIP_TRY(c, hipMemcpyAsync(out, c->dt_text, (size_t)n, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return WK_OK;
+}
+
+// ---- gzip members inflated on the device (wk_dinflate.hpp) ---------------------------------------
+// Spans that the kernel may be given: streams inside the blob with room for a trailer, sizes that fit 31 bits.
+static int dinf_check_spans(wk_ctx* c, int64_t n_blob, const int64_t* lo, const int64_t* hi, const int64_t* off, int64_t n) {
+    if (off[0] != 0) return fail(c, WK_E_ARG, "off[0] is not 0");
+    for (int64_t i = 0; i < n; ++i) {
+        if (lo[i] < 0 || hi[i] > n_blob || hi[i] - lo[i] < 8 || hi[i] - lo[i] >= (1ll << 31))
+            return fail(c, WK_E_ARG, "member %lld: compressed span [%lld, %lld) is not inside the %lld bytes given", (long long)i,
+                        (long long)lo[i], (long long)hi[i], (long long)n_blob);
+        if (off[i + 1] < off[i] || off[i + 1] - off[i] >= (1ll << 31))
+            return fail(c, WK_E_ARG, "member %lld: a size of %lld bytes", (long long)i, (long long)(off[i + 1] - off[i]));
+    }
+    return WK_OK;
+}
+
+// d_meta: lo[n], hi[n], off[n + 1]; d_status: n words, then "any failed" and the hand-out counter
+static void dinf_launch(wk_ctx* c, const unsigned char* d_blob, const int64_t* d_meta, int64_t n, unsigned char* d_out, uint32_t* d_status,
+                        hipStream_t s) {
+    const unsigned grid = (unsigned)std::min<int64_t>(n, (int64_t)c->prop.multiProcessorCount * kDinfWavesPerCu);
+    hipLaunchKernelGGL(dinflate_kernel, dim3(grid), dim3(64), 0, s, d_blob, d_meta, d_meta + n, d_meta + 2 * n, (uint32_t)n, d_out, d_status,
+                       d_status + n, d_status + n + 1);
+}
+
+int wk_inflate_members_device(wk_ctx* c, const char* blob, int64_t n_blob, const int64_t* lo, const int64_t* hi, const int64_t* off, int64_t n,
+                              char* out, uint32_t* status) {
+    if (!c || !blob || n_blob <= 0 || !lo || !hi || !off || n <= 0 || n >= (1ll << 31) || !status) return WK_E_ARG;
+    if (int rc = dinf_check_spans(c, n_blob, lo, hi, off, n)) return rc;
+    const int64_t total = off[n];
+    if (total && !out) return WK_E_ARG;
+    DeviceGuard guard(c->device);
+    constexpr size_t kGuard = 256;
+    HIP_TRY(c, c->di_blob.reserve((size_t)n_blob));
+    HIP_TRY(c, c->di_meta.reserve((size_t)(3 * n + 1) * 8));
+    HIP_TRY(c, c->di_out.reserve((size_t)total + 2 * kGuard));
+    HIP_TRY(c, c->di_status.reserve((size_t)(n + 2) * 4));
+    unsigned char* d_out = c->di_out.as<unsigned char>();
+    int64_t* d_meta = c->di_meta.as<int64_t>();
+    HIP_TRY(c, hipMemcpyAsync(c->di_blob.p, blob, (size_t)n_blob, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_meta, lo, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_meta + n, hi, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_meta + 2 * n, off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(d_out, 0xA5, (size_t)total + 2 * kGuard, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->di_status.p, 0, (size_t)(n + 2) * 4, c->stream));
+    dinf_launch(c, c->di_blob.as<unsigned char>(), d_meta, n, d_out + kGuard, c->di_status.as<uint32_t>(), c->stream);
+    HIP_TRY(c, hipGetLastError());
+    unsigned char edge[2 * kGuard];
+    HIP_TRY(c, hipMemcpyAsync(edge, d_out, kGuard, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(edge + kGuard, d_out + kGuard + total, kGuard, hipMemcpyDeviceToHost, c->stream));
+    if (total) HIP_TRY(c, hipMemcpyAsync(out, d_out + kGuard, (size_t)total, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(status, c->di_status.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    uint32_t any = 0;
+    HIP_TRY(c, hipMemcpyAsync(&any, c->di_status.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < 2 * kGuard; ++i)
+        if (edge[i] != 0xA5) return fail(c, WK_E_STATE, "the inflate kernel wrote outside the text (guard byte %zu)", i);
+    bool failed = false;
+    for (int64_t i = 0; i < n; ++i) failed = failed || status[i] != 0;
+    if (failed != (any != 0)) return fail(c, WK_E_STATE, "the inflate kernel's failure word (%u) does not match its status words", any);
     return WK_OK;
 }
 

@@ -60,6 +60,7 @@ class GunzipStream(io.RawIOBase):
         from . import _native
         super().__init__()
         self._gz = _native.Gunzip(fp, threads)
+        self.path = fp          # (the device text route maps a chain of members itself)
         self._buf = memoryview(b'')
         self._eof = False
         self.threads = threads

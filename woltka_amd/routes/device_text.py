@@ -361,6 +361,8 @@ class _TextAhead:
                             t, s2 = inflight.popleft()
                             ctx.dtok_copy_wait(t)
                             ring.release(s2)
+                    elif isinstance(slot, tuple) and slot[0] == 'det':
+                        pass            # (inflated on the device: the generator issued it)
                     else:               # (a file pinned in place: it stays)
                         ctx.dtok_copy(out, begin, stop)
                     lap['copy'] += time.perf_counter() - t0
@@ -671,6 +673,8 @@ class DeviceTextRoute:
     DTOK_READ_PIECE = int(os.environ.get('WOLTKA_READ_PIECE', 8 << 20))   # bytes per pread of the block reader's threads
     DTOK_AHEAD = int(os.environ.get('WOLTKA_TEXT_AHEAD', 160))     # blocks copied to the device ahead of the one being scanned (at most wk_ctx::kTextBufs - 1) by the reader that starts before the hierarchy is read
     DTOK_DEPTH = int(os.environ.get('WOLTKA_TEXT_DEPTH', 6))       # ... by a reader the engine starts when a file's turn comes: the scans follow at once, a deeper queue only takes the CPUs from whoever else works (config 5's second call: 2.11 s with 3, 2.17 with 160, tools/ab_text_ahead.sh)
+    DINFLATE_MEMBERS = 1024     # gzip members per block inflated on the device: the waves resident at once (256 CUs x 4, csrc/wk_dinflate.hpp) -- one more than that and the kernel takes twice as long
+    DINFLATE_MEMBER_MAX = 1 << 17   # mean bytes of text per member above which a chain is left to the host inflater
     DTOK_HEADROOM = 1 << 20     # room in front of a block's bytes for the run the block before left unfinished
     HOSTREG_PIECE = 256 << 20   # a file is pinned in place in pieces of this size (a multiple of the page size)
     HOSTREG_MIN = 64 << 20      # smaller files are read into pinned buffers
@@ -844,6 +848,188 @@ class DeviceTextRoute:
                     ring.release(s2)
                 pool.shutdown(wait=True)
 
+        def open_members():
+            """The compressed file behind `source` as (bytes, start, lo, hi,
+            ISIZE) if it is a chain of members that state their size (BGZF,
+            'WK': `wk_gz_walk_members`), else None -- the file goes through
+            `blocks_stream` then.  ``WOLTKA_NO_DINFLATE=1``: always None."""
+            path = getattr(source, 'path', None)
+            if path is None or os.environ.get('WOLTKA_NO_DINFLATE'):
+                return None
+            import mmap
+            try:
+                with open(path, 'rb') as f:
+                    mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+            except (OSError, ValueError):
+                return None
+            arr = np.frombuffer(mm, dtype=np.uint8)
+            walk = nat.gz_walk_members(arr)
+            if walk is None or not walk[0].size:
+                return None
+            # (one wave inflates one member at some 13 MB/s: members of 1 MB,
+            # 64 to a block, would leave most of the device idle -- such a
+            # chain stays with the host's threads)
+            if walk[3].mean() > self.DINFLATE_MEMBER_MAX:
+                return None
+            return (arr,) + walk
+
+        def blocks_members(chain):
+            # The same cut for a chain of gzip members that state their size:
+            # a block is the next run of members whose text fits; only their
+            # compressed bytes cross the link, and the device inflates them
+            # behind the carry (`wk_dtok_inflate_ahead`, csrc/wk_dinflate.hpp).
+            # The host inflates the block's last member(s) alone, to find the
+            # start of the last run of equal query ids; what lies behind it is
+            # the next block's carry.  Header lines (and a run longer than a
+            # block) go the way of `blocks_stream`'s slow path: inflated on the
+            # host, copied by the scan.
+            arr, _, lo, hi, isz = chain
+            H = self.DTOK_HEADROOM
+            nm = lo.size
+            csum = np.zeros(nm + 1, dtype=np.int64)
+            np.cumsum(isz, out=csum[1:])
+            threads = max(1, tokenizer_threads())
+
+            def text_of(a, b):
+                return nat.gz_inflate_streams(
+                    arr, lo[a:b], hi[a:b], isz[a:b],
+                    threads if b - a > 4 else 1)
+
+            prev = []           # the block inflating on the device: (ticket, slot, item)
+
+            def settle_prev():
+                if not prev:
+                    return None
+                ticket, slot, item = prev.pop()
+                try:
+                    self.ctx.dtok_copy_wait(ticket)     # (OSError: a damaged member)
+                finally:
+                    ring.release(slot)
+                return item
+
+            carry, in_header, first = b'', True, True
+            ramp = None if getattr(tok, 'warm', False) else min(block, 1 << 20)
+            span = ramp or block
+            m, h_span = 0, min(block, 1 << 16)
+            try:
+                while m < nm or carry:
+                    # (header lines go through the host: no more of the file
+                    # with them than it takes to see them end)
+                    want = min(span, h_span) if in_header else span
+                    room = max(int(want) - len(carry), 1)
+                    e = int(np.searchsorted(csum, csum[m] + room, 'right')) - 1
+                    e = min(nm, max(e, m + 1))
+                    if not in_header:   # (one round of the device's waves)
+                        e = min(e, m + self.DINFLATE_MEMBERS)
+                    final = e >= nm
+                    n_text = int(csum[e] - csum[m])
+                    total = len(carry) + n_text
+                    n_comp = int(hi[e - 1] - lo[m]) if e > m else 0
+                    cut = None
+                    if not in_header and e > m and span <= block and \
+                            len(carry) <= H and n_comp <= block + H and \
+                            total < (1 << 31) - 64:
+                        # the cut, from the block's tail alone
+                        t = e - 1
+                        while True:
+                            t0 = time.perf_counter()
+                            tail = text_of(t, e)
+                            if t == m:
+                                view = np.concatenate([np.frombuffer(
+                                    carry, dtype=np.uint8), tail]) \
+                                    if carry else tail
+                                skip = 0
+                            else:
+                                nl = np.flatnonzero(tail[:1 << 16] == 10)
+                                if not nl.size:
+                                    nl = np.flatnonzero(tail == 10)
+                                skip = int(nl[0]) + 1 if nl.size else tail.size
+                                view = tail[skip:]
+                            lap['read'] += time.perf_counter() - t0
+                            t0 = time.perf_counter()
+                            ok, begin, stop, hdr = (False, 0, 0, False) \
+                                if not view.size else nat.Tokenizer.sam_span(
+                                    view, final, False, self._dfmt, ex)
+                            lap['span'] += time.perf_counter() - t0
+                            if ok and begin == 0 and (stop > 0 or final) and \
+                                    not hdr:
+                                cut = total - view.size + stop
+                                behind = view[stop:].tobytes()
+                                last = int(view[stop - 1]) if stop else 10
+                                break
+                            if t == m:
+                                break
+                            t = max(m, e - 2 * (e - t))
+                    if cut is not None and cut > 0:
+                        bufs = ring.current()
+                        buf, slot = bufs['text'], ring.take()
+                        a = int(lo[m])
+                        buf[:n_comp] = arr[a:a + n_comp]
+                        try:
+                            ticket = self.ctx.dtok_inflate_ahead(
+                                buf, n_comp, lo[m:e] - a, hi[m:e] - a,
+                                csum[m:e + 1] - csum[m], carry, cut, last)
+                        except BaseException:
+                            ring.release(slot)
+                            raise
+                        ROUTES['dinflate'] += 1
+                        item = (('det', b'', b'' if final else behind), buf,
+                                total if not final else cut, 0, cut, first,
+                                final, False, False)
+                        ready = settle_prev()
+                        prev.append((ticket, slot, item))
+                        if ready is not None:
+                            yield ready
+                        if ramp is not None:
+                            ramp = min(block, ramp * 4)
+                            if ramp == block:
+                                tok.warm, ramp = True, None
+                        span = ramp or block
+                        carry, first, m = (b'' if final else behind), False, e
+                        if final:
+                            break
+                        continue
+                    # through the host: header lines, a long run, a block too
+                    # large for a pinned buffer
+                    ready = settle_prev()
+                    if ready is not None:
+                        yield ready
+                    t0 = time.perf_counter()
+                    text = text_of(m, e)
+                    out = np.concatenate([np.frombuffer(carry, dtype=np.uint8),
+                                          text]) if carry else text
+                    lap['read'] += time.perf_counter() - t0
+                    t0 = time.perf_counter()
+                    ok, begin, stop, hdr = nat.Tokenizer.sam_span(
+                        out, final, in_header, self._dfmt, ex)
+                    lap['span'] += time.perf_counter() - t0
+                    if (not ok or (stop == 0 and out.size)) and not final:
+                        span = max(span, total) * 2     # no complete run yet
+                        h_span = span
+                        continue
+                    if in_header and hdr:
+                        h_span = min(block, h_span * 2)
+                    elif ramp is not None:
+                        ramp = min(block, ramp * 4)
+                        if ramp == block:
+                            tok.warm, ramp = True, None
+                    span = ramp or block
+                    carry = b'' if final else out[stop:].tobytes()
+                    yield None, out, out.size, begin, stop, first, final, \
+                        in_header, hdr
+                    in_header, first, m = hdr, False, e
+                    if final:
+                        break
+                ready = settle_prev()
+                if ready is not None:
+                    yield ready
+            finally:
+                while prev:
+                    try:
+                        settle_prev()
+                    except Exception:   # noqa: BLE001 - already on its way out
+                        pass
+
         # The same blocks without a copy on the host: the file mapped read-only
         # and pinned in place piece by piece (wk_host_register), so that the
         # device copies the text straight from the page cache.  The host then
@@ -911,7 +1097,9 @@ class DeviceTextRoute:
                 dev_id = os.fstat(fd).st_dev
             except OSError:
                 dev_id = None
-            if _HOSTREG_SLOW.get(dev_id) and not os.environ.get('WOLTKA_HOSTREG'):
+            # (slow = below HOSTREG_RATE: with a rate of 0 nothing is)
+            if _HOSTREG_SLOW.get(dev_id) and self.HOSTREG_RATE > 0 and \
+                    not os.environ.get('WOLTKA_HOSTREG'):
                 return None
             import mmap
             try:
@@ -1046,7 +1234,12 @@ class DeviceTextRoute:
         ahead, whole = taken, None
         if ahead is None:
             whole = open_mapped() if source is None else None
-            if source is not None:
+            chain = open_members() if source is not None else None
+            if chain is not None:
+                # (the stream's own inflater, which decodes ahead, is not needed)
+                source.close()
+                gen = blocks_members(chain)
+            elif source is not None:
                 gen = blocks_stream()
             elif whole is not None:
                 gen = blocks_mapped(whole)
@@ -1063,7 +1256,9 @@ class DeviceTextRoute:
                                3 if whole is not None else self.DTOK_DEPTH,
                                lap)
         # (a plain file's size tells how many records its sample will hold)
-        self.ctx.dtok_expect(size - start if source is None else 0)
+        self.ctx.dtok_expect(size - start if source is None else
+                             int(chain[4].sum()) if taken is None and
+                             chain is not None else 0)
 
         # While blocks go through the one-kernel tokenizer their verdicts are
         # read one block late (`wk_dtok_scan_emit_begin` / `_end`): the next
