@@ -51,7 +51,13 @@ extern "C" {
  * log; 0 = as few as the merge's LDS array allows), "stripes" (0: the
  * coord-match tally never sorts the hits by genome stripe, csrc/wk_stripe.hpp)
  * and "stripes_min" (chunks of fewer hits keep the gather kernels; default
- * 4,000,000). */
+ * 4,000,000).
+ * "weigh_wide" (0/1; 1: a fresh accumulation of packed records opens unsliced
+ * and its flush takes the wide layout of the weighted histogram,
+ * csrc/wk_weigh_wide.hpp, at any table size; 0, the default: only where the
+ * table has more slices than a team has workgroups, 32 on a whole device) and
+ * "weigh_wide_wgs" (workgroups of that layout's histogram, at most; 0 = one
+ * per CU, up to 1,024). */
 int wk_tune(wk_ctx* ctx, const char* name, int64_t value);
 
 /* ---- measurement ------------------------------------------------------- */
@@ -60,7 +66,8 @@ int wk_tune(wk_ctx* ctx, const char* name, int64_t value);
  * wk_timer_ms returns the elapsed GPU time of the last closed region.
  * wk_last_kernel_ms returns the duration of the most recent launch of the
  * named kernel family ("classify", "leftover", "weigh_merge", "read_sizes", "dense_merge", "partition_merge",
- * "match_count", "match_write", "scan", "rank_table", "compact"), measured with events around that launch; event
+ * "match_count", "match_write", "scan", "rank_table", "compact", "weigh_wide_part": count, scan and scatter of the wide
+ * layout, "weigh_wide": its histogram), measured with events around that launch; event
  * recording around individual kernels is enabled by wk_profile_kernels(1). */
 int wk_timer_begin(wk_ctx* ctx);
 int wk_timer_end(wk_ctx* ctx);

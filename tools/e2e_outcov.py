@@ -10,11 +10,9 @@ bench.py / tools/native/libwk_synth.so, in the page cache; two depths:
               than the rows (whole-genome SAM against a few hundred genomes)
     shallow   1 M subjects of 5 Mb, a few rows each: the merged set is about
               as large as the rows -- the spill path's worst case (and a .cov
-              line per record to write).  `--subjects N` sets another number:
-              the weighted histogram of the plain device text route takes
-              subject tables up to ~1.3 M (32 slices of 40 k bins), so config
-              3's 2 M *nodes* as subjects do not run there, with or without
-              `--outcov`
+              line per record to write).  `--subjects N` sets another number
+              (up to the packed record's 2^23; tables beyond 1 299 456 go
+              through the wide layout of the weighted histogram)
 
     python tools/e2e_outcov.py --records 50000000 --reps 5 \
         --json profiles/outcov_e2e.json

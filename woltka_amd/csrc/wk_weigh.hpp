@@ -484,6 +484,7 @@ struct WeighMergeArgs {
     CountTable table;
     uint32_t streams;                    // > 0: the slab of weigh_streams_kernel (rows of kSliceBins, per stream wg_first)
     uint32_t wg_first[kMaxStreams + 1];
+    const uint32_t* wide_first;          // the same per bucket of the wide layout (wk_weigh_wide.hpp), in HBM; or null
 };
 
 // 128 subjects per workgroup, eight threads each: a thread sums every eighth row of
@@ -501,7 +502,14 @@ __global__ void __launch_bounds__(1024) weigh_merge_kernel(WeighMergeArgs a, uin
     const uint32_t i = blockIdx.x * kMergeSubjects + sub;
     unsigned long long w = 0;
     if (i < a.n_subjects) {
-        if (a.streams) {
+        if (a.wide_first) {
+            const uint32_t k = i / kSliceBins, colm = i - k * kSliceBins;
+            const uint32_t first = a.wide_first[k];
+            const uint32_t* p = a.slab + (size_t)first * kSliceBins + colm;
+            const uint32_t rows = a.wide_first[k + 1] - first;
+#pragma unroll 4
+            for (uint32_t t = g; t < rows; t += kMergeParts) w += p[(size_t)t * kSliceBins];
+        } else if (a.streams) {
             const uint32_t k = i / kSliceBins, colm = i - k * kSliceBins;
             const uint32_t* p = a.slab + (size_t)a.wg_first[k] * kSliceBins + colm;
             const uint32_t rows = a.wg_first[k + 1] - a.wg_first[k];

@@ -31,6 +31,7 @@
 #include "wk_readmap.hpp"
 #include "wk_tok_internal.h"
 #include "wk_weigh.hpp"
+#include "wk_weigh_wide.hpp"
 #include "wk_sized.hpp"
 #include "wk_logred.hpp"
 #include "wk_dinflate.hpp"
@@ -239,6 +240,10 @@ struct wk_ctx {
     bool listed_only = false;  // wk_classify_staged evaluates only the reads of left_mask
     int bins_ring = 4;  // measurement knob: load stages in flight of weigh_bins_kernel
     DevBuf w_slab, w_hi, w_invalid;
+    // the wide layout (wk_weigh_wide.hpp): the records by bucket; the plan, the buckets' counts and their cursors
+    DevBuf w_wide, w_wide_plan;
+    int weigh_wide = 0;      // measurement knob: 1 = a fresh accumulation opens unsliced and its flush takes the wide layout
+    int weigh_wide_wgs = 0;  // measurement knob: workgroups of the wide histogram, at most (0: one per CU)
     size_t w_hi_clean = 0;        // leading entries of w_hi known to be zero
     // size-normalised plain jobs (wk_sized.hpp): rows {feature, subject feature, job << 16 | divisor, group} and their
     // counts, appended by every flush of such a job set until wk_sized_fetch takes them
@@ -1039,6 +1044,8 @@ int wk_create(int device, wk_ctx** out) {
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBinsMaxLds)) != hipSuccess ||
         (e = hipFuncSetAttribute(reinterpret_cast<const void*>(&weigh_streams_kernel<8>),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBinsMaxLds)) != hipSuccess ||
+        (e = hipFuncSetAttribute(reinterpret_cast<const void*>(&weigh_wide_kernel<4>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBinsMaxLds)) != hipSuccess ||
         (e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sized_bins_kernel<4>),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBinsMaxLds)) != hipSuccess ||
         (e = hipFuncSetAttribute(reinterpret_cast<const void*>(&weigh_merge_kernel),
@@ -1083,6 +1090,8 @@ void wk_destroy(wk_ctx* c) {
     c->c_words.release();
     for (DevBuf* b : {&c->di_blob, &c->di_meta, &c->di_out, &c->di_status}) b->release();
     for (DevBuf& b : c->w_stream) b.release();
+    c->w_wide.release();
+    c->w_wide_plan.release();
     c->w_backup2.release();
     c->w_backup3.release();
     for (hipEvent_t& e : c->lag_ev)
@@ -1340,6 +1349,16 @@ int wk_tune(wk_ctx* c, const char* name, int64_t value) {
     }
     if (!strcmp(name, "words_keep")) {
         c->words_keep = value ? 1 : 0;
+        return WK_OK;
+    }
+    if (!strcmp(name, "weigh_wide")) {
+        if (value != 0 && value != 1) return fail(c, WK_E_ARG, "weigh_wide must be 0 or 1");
+        c->weigh_wide = (int)value;
+        return WK_OK;
+    }
+    if (!strcmp(name, "weigh_wide_wgs")) {
+        if (value < 0 || value > (int64_t)kWideMaxWgs) return fail(c, WK_E_ARG, "weigh_wide_wgs must be in [0, %u]", kWideMaxWgs);
+        c->weigh_wide_wgs = (int)value;
         return WK_OK;
     }
     if (!strcmp(name, "bins_ring")) {
@@ -2478,6 +2497,13 @@ int wk_log_reduce(wk_ctx* c, int64_t* n_rows_in, int64_t* n_distinct) {
     return WK_OK;
 }
 
+// teams per XCD of the team layout over the unsliced stream; 0: the table has more slices than a team has workgroups
+static uint32_t words_team_size(const wk_ctx* c) {
+    const uint32_t cus = (uint32_t)c->prop.multiProcessorCount;
+    const uint32_t w_xcd = cus % 8u ? 1u : 8u;
+    return (cus / w_xcd) / (uint32_t)streams_needed(c);
+}
+
 int wk_words_flush(wk_ctx* c) {
     if (!c) return WK_E_ARG;
     if (c->lag_count) return fail(c, WK_E_STATE, "blocks whose verdict has not been read (wk_dtok_scan_emit_end)");
@@ -2662,6 +2688,47 @@ int wk_words_flush(wk_ctx* c) {
         for (int k = 0; k <= kMaxStreams; ++k) wm.wg_first[k] = sa.wg_first[k];
         wm.bins = kSliceBins;
         wm.n_teams = 0;
+    } else if (c->weigh_wide || words_team_size(c) == 0) {
+        // ---- more slices than a team has workgroups (wk_weigh_wide.hpp): the one stream partitioned by slice, then every
+        // bucket read once
+        if (c->w_count[0] >= (1ull << 30)) return fail(c, WK_E_RANGE, "more than 2^30 records in one stream");
+        const uint32_t n = (uint32_t)c->w_count[0];
+        const uint32_t n_buckets = (uint32_t)streams_needed(c);  // (at most kWideMaxBuckets: words_jobs_ok)
+        const uint32_t n_wg = std::min(c->weigh_wide_wgs > 0 ? (uint32_t)c->weigh_wide_wgs : cus, kWideMaxWgs);
+        const uint32_t slab_rows = n_wg + n_buckets;
+        const size_t room = (size_t)wide_room(n);
+        const size_t plan_bytes = (sizeof(WidePlan) + 127) & ~(size_t)127;
+        HIP_TRY(c, c->w_wide.reserve(room * 4));
+        HIP_TRY(c, c->w_wide_plan.reserve(plan_bytes + 1024 + (size_t)kWideMaxBuckets * kWideCursorPad * 4));
+        HIP_TRY(c, c->w_slab.reserve((size_t)slab_rows * kSliceBins * 4));
+        WidePlan* plan = reinterpret_cast<WidePlan*>(c->w_wide_plan.p);
+        uint32_t* bucket_count = reinterpret_cast<uint32_t*>(static_cast<char*>(c->w_wide_plan.p) + plan_bytes);
+        uint32_t* cursor = bucket_count + 256;
+        HIP_TRY(c, hipMemsetAsync(bucket_count, 0, 1024, c->stream));
+        const uint32_t n_tiles = (n + kWideTile - 1u) / kWideTile;
+        const dim3 pgrid(std::max(1u, std::min(n_tiles, 2u * cus)));
+        kt = ktimer_begin(c, "weigh_wide_part");
+        hipLaunchKernelGGL(wide_count_kernel, pgrid, dim3(kWideThreads), 0, c->stream, c->w_stream[0].as<uint32_t>(), n, n_buckets, bucket_count);
+        hipLaunchKernelGGL(wide_scan_kernel, dim3(1), dim3(256), 0, c->stream, bucket_count, n_buckets, n_wg, plan, cursor);
+        hipLaunchKernelGGL(wide_scatter_kernel, pgrid, dim3(kWideThreads), 0, c->stream, c->w_stream[0].as<uint32_t>(), n, n_buckets, cursor,
+                           c->w_wide.as<uint32_t>(), (uint32_t)std::min<size_t>(room, 0xFFFFFFFFu));
+        ktimer_end(c, kt);
+        WideBinsArgs wa{};
+        wa.words = c->w_wide.as<uint32_t>();
+        wa.plan = plan;
+        wa.n_subjects = (uint32_t)c->n_subjects;
+        wa.slab = c->w_slab.as<uint32_t>();
+        wa.slab_rows = slab_rows;
+        wa.hi = c->w_hi.as<uint32_t>();
+        wa.err = scalar_err(c);
+        kt = ktimer_begin(c, "weigh_wide");
+        hipLaunchKernelGGL((weigh_wide_kernel<4>), dim3(n_wg), dim3(kWeighThreads), kBinsMaxLds, c->stream, wa);
+        ktimer_end(c, kt);
+        wm.slab = wa.slab;
+        wm.hi = wa.hi;
+        wm.wide_first = plan->item_first;
+        wm.bins = kSliceBins;
+        wm.n_teams = 0;
     } else {
         // ---- more slices than streams: one stream, a team of workgroups per tile (round 3's launch)
         uint32_t w_xcd = 8;
@@ -2669,8 +2736,7 @@ int wk_words_flush(wk_ctx* c) {
         const int64_t cap = (int64_t)kBinsMaxLds / 4 - 96;
         const uint32_t w_slices = (uint32_t)((c->n_subjects + cap - 1) / cap);
         const uint32_t w_bins = ((uint32_t)c->n_subjects + w_slices - 1) / w_slices;
-        const uint32_t w_teams = (cus / w_xcd) / w_slices;
-        if (!w_teams) return fail(c, WK_E_RANGE, "subject table too large for the weighted histogram");
+        const uint32_t w_teams = words_team_size(c);
         const uint32_t n_teams = w_xcd * w_teams;
         HIP_TRY(c, c->w_slab.reserve((size_t)w_slices * n_teams * w_bins * 4));
         BinsArgs ba{};
@@ -2748,7 +2814,7 @@ int wk_words_begin(wk_ctx* c, const wk_job* jobs, int32_t n_jobs, int32_t group,
     }
     if (!c->w_open || c->w_records == 0) {  // a fresh accumulation
         if ((rc = words_reset(c))) return rc;
-        c->w_sliced = mode == 0 && c->use_streams && streams_needed(c) <= kMaxStreams;
+        c->w_sliced = mode == 0 && c->use_streams && !c->weigh_wide && streams_needed(c) <= kMaxStreams;
         c->w_streams = 0;
     }
     c->w_jobs.assign(jobs, jobs + n_jobs);
