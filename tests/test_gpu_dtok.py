@@ -1081,6 +1081,120 @@ def test_late_verdict_entry_points_keep_their_contract():
             wl.close()
 
 
+def test_late_verdict_takes_the_older_of_two_copies_with_one_tag():
+    """`wk_dtok_scan_emit_begin` finds a block copied ahead by its tag (address,
+    length).  A reader that reuses one pinned buffer copies blocks of one
+    length from one address: of two such copies the older is the block asked
+    for first (`test_text_back...` pins the same rule for `wk_dtok_scan`).
+    Two blocks of equal length and different read counts, copied ahead from
+    one address, come out in the order they were copied, and the sample has
+    the cells of the two-call pass over the same text."""
+    from woltka_amd import _native as nat
+    from woltka_amd import synth
+    tp = synth.as_sets(synth.lca_problem(
+        np.random.default_rng(1), n_nodes=5000, n_subjects=500, n_reads=4000))
+    th = tp['hier']
+    names = [b'T%07d' % s for s in np.unique(tp['subj']).tolist()[:7]]
+
+    def sam(k, per_read, step):
+        # 300 lines of one width; `per_read` lines in a row share a read id
+        # and name different subjects
+        return b''.join(
+            b'q%d%05d\t0\t%s\t1\t1\t5M\t*\t0\t0\t*\t*\n' % (
+                k, i // per_read,
+                names[(i // per_read * step + i % per_read * (k + 1)) % 7])
+            for i in range(300))
+
+    texts = [sam(0, 1, 1), sam(1, 3, 2), sam(2, 1, 3), sam(3, 2, 5)]
+    reads = [300, 100, 300, 150]
+    assert len(set(map(len, texts))) == 1 and texts[2] != texts[3]
+    n = len(texts[0])
+    job = [nat.Job(nat.MODE_RANK, 0, 0, 0, 0.0)]
+
+    def two_calls(ctx, tok, buf, size):
+        status, n_lines = ctx.dtok_scan(tok, buf, 0, size)
+        assert (status, n_lines) == (0, size // n * 300)
+        fresh = tok.new_subjects()
+        assert len(fresh) == 7
+        ctx.set_subjects(np.asarray([int(x[1:8]) for x in fresh], np.int32))
+        assert ctx.words_begin(job, 0)
+        st, n_reads, _ = ctx.dtok_emit()
+        assert st == 0
+        return n_reads
+
+    def cells(ctx):
+        keys, vals = ctx.counts_fetch()
+        o = np.argsort(keys, kind='stable')
+        return keys[o].tolist(), vals[o].tolist()
+
+    def context():
+        ctx = nat.Context(0)
+        ctx.set_tree(th.parent, th.last, th.rank_code)
+        ctx.build_rank_table(0, th.rank_codes['genus'])
+        ctx.counts_reserve(1 << 16)
+        ctx.dtok_format('sam')
+        return ctx, nat.Tokenizer(2)
+
+    ctx, tok = context()
+    try:
+        whole = np.frombuffer(b''.join(texts), dtype=np.uint8)
+        assert two_calls(ctx, tok, whole, whole.size) == sum(reads)
+        ctx.words_flush()
+        expected = cells(ctx)
+    finally:
+        tok.close()
+        ctx.close()
+
+    ctx, tok = context()
+    try:
+        pinned = ctx.host_alloc(1 << 16, np.uint8)
+        pinned[:n] = np.frombuffer(texts[0], dtype=np.uint8)
+        assert two_calls(ctx, tok, pinned, n) == reads[0]
+        # the first block the one kernel keeps: the lines per byte that
+        # `_begin` sizes a block copied ahead by
+        before = ctx.dtok_fused_counts()
+        pinned[:n] = np.frombuffer(texts[1], dtype=np.uint8)
+        status, n_lines, done = ctx.dtok_scan_emit(tok, pinned, 0, n)
+        assert (status, n_lines, done) == (0, 300, reads[1])
+        assert ctx.dtok_fused_counts()[0] == before[0] + 1
+        tickets = []
+        for t in texts[2:]:
+            pinned[:n] = np.frombuffer(t, dtype=np.uint8)
+            tk = ctx.dtok_copy_ahead(pinned, 0, n)
+            ctx.dtok_copy_wait(tk)
+            tickets.append(tk)
+        assert len(set(tickets)) == 2
+        pinned[:] = 0
+        got, under_way, accepted = [], 0, 0
+
+        def settle():
+            nonlocal under_way
+            while under_way:
+                res = ctx.dtok_scan_emit_end()
+                assert res is not None
+                got.append(res)
+                under_way -= 1
+
+        for _ in texts[2:]:
+            if ctx.dtok_scan_emit_begin(tok, pinned, 0, n):
+                under_way += 1
+                accepted += 1
+                continue
+            settle()
+            status, n_lines, done = ctx.dtok_scan_emit(tok, pinned, 0, n)
+            assert status == 0 and done is not None
+            got.append((n_lines, done))
+        settle()
+        ctx.words_flush()
+        assert accepted >= 1
+        assert got == [(300, reads[2]), (300, reads[3])]
+        assert not tok.new_subjects()
+        assert cells(ctx) == expected
+    finally:
+        tok.close()
+        ctx.close()
+
+
 def test_piled_hits_entry_point_keeps_its_contract():
     """`wk_dtok_stage_hits_append` by itself (include/woltka_hip.h): a pile that
     has not been counted is staged over by nothing else (WK_E_STATE), a block

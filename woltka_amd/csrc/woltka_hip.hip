@@ -89,6 +89,37 @@ struct KernelTimer {
     bool valid = false;
 };
 
+// One buffer of block text on the device (wk_ctx::text_buf) and what belongs to the block it holds.  A buffer is free,
+// holds a block copied ahead (tagged by `src` / `n`), is the one the kernels of the block scanned last read (until
+// the next scan begins), or is read by a block whose verdict is still out (wk_dtok_scan_emit_begin).  wk_dtok_copy
+// may be called from another thread than the scans (the host layer's reader thread issues the copies as soon as a
+// block is cut): `state` and the tag -- `src`, `n`, `seq` -- are guarded by wk_ctx::copy_mu.  `counted`, `detached` and
+// `last` describe the tagged block: written before the tag is, read once it has been found.  The rest belongs to
+// whoever holds the buffer by its state.
+struct TextBuf {
+    unsigned char state = 0;       // wk_ctx::kBufFree ...
+    const char* src = nullptr;     // the tag: host address and length of the block
+    uint32_t n = 0;
+    unsigned long long seq = 0;    // blocks are scanned in the order they were copied: a copy's number tells two buffers with the same tag apart
+    bool counted = false;          // the block's newlines were counted behind its copy (`tiles`, `tile_off`, wk_ctx::copy_newlines[k])
+    // a block copied by wk_dtok_copy_ahead: the host bytes are not kept until the scan (the reader reuses its pinned
+    // buffer once the copy is through); what the scan wants from them comes back from the device when it does
+    bool detached = false;
+    char last = 0;                 // the block's last byte (a last line without newline)
+    hipEvent_t ev0 = nullptr;      // start of the block's copy
+    hipEvent_t evm = nullptr;      // ... its end (the newline count behind it runs on a stream of its own)
+    hipEvent_t ev = nullptr;       // ... and the end of that count
+    unsigned char* text = nullptr; // the device memory: a share of a slab, or `own` (text_buffer())
+    DevBuf own;
+    DevBuf tiles, tile_off;        // newlines per tile of a block copied ahead, counted behind its copy
+    // a block wk_dtok_inflate_ahead fills: compressed bytes, members' spans and status words (wk_dinflate.hpp); the
+    // kernel's "a member failed" word lands in wk_ctx::di_any_host[k] (read by wk_dtok_copy_wait)
+    DevBuf di_comp, di_meta, di_status;
+    bool di_used = false;
+    std::vector<int64_t> di_meta_host;   // what the copies of the block's spans and carry read until they are through
+    std::vector<char> di_carry_host;
+};
+
 }  // namespace
 
 struct wk_ctx {
@@ -216,8 +247,6 @@ struct wk_ctx {
     double lap_c[5] = {0, 0, 0, 0, 0};  // ... of the copy: streams + events / device buffer / copy queued / count queued; [4] the longest device-buffer step
     double lap_copy_ms = 0;           // ... and the copies' own durations (events around each on the copy stream)
     int64_t lap_copy_bytes = 0;
-    hipEvent_t copy_ev0[192] = {};    // (kTextBufs) start of a block's copy
-    hipEvent_t copy_evm[192] = {};    // ... its end (the newline count behind it runs on a stream of its own)
 
     int lds_slots = 8192;  // LDS front-cache slots per workgroup (16 B each = 128 KiB)
     int threads = 1024;    // workgroup size of the direct classify kernel
@@ -292,7 +321,6 @@ struct wk_ctx {
     bool lag_poll = true;           // a block's end is seen in pinned memory instead of waited for through an event (WOLTKA_LAG_POLL=0: the event; 127.7 against 126.3 us per block, tools/lag_probe.py)
     uint32_t lag_seq = 0;
     bool lag_enabled = true;        // (WOLTKA_NO_LAG=1: every block's verdict is read before the next is launched)
-    bool fz_no_chain = false;       // (measurement, WOLTKA_FZ_NO_CHAIN=1: the small kernel in front of every block)
     int w_streams = 0;              // streams the open accumulation writes to
     bool w_sliced = false;
     bool w_counts_known = false;    // w_count holds the cursors' values
@@ -325,15 +353,22 @@ struct wk_ctx {
     // being read) and then runs as far ahead as it likes -- HBM is what a 288 GB device has to spare; the
     // buffers are allocated as they are first used, the lowest free one first
     static constexpr int kTextBufs = 192;
-    static_assert(sizeof(copy_ev0) / sizeof(copy_ev0[0]) == kTextBufs, "copy_ev0 has kTextBufs entries");
     // (text buffers are cut from slabs of kSlabBufs: one hipMalloc per GB instead of one per block while the reader
     // runs ahead -- every allocation holds the runtime's lock against the launches of the scans; a block larger than a
-    // slab's share gets a buffer of its own, d_textbuf[k])
+    // slab's share gets a buffer of its own, TextBuf::own)
     static constexpr int kSlabBufs = 16;
     static constexpr size_t kTextStride = ((size_t)66 << 20) + 256;
     DevBuf d_textslab[kTextBufs / kSlabBufs];
-    unsigned char* d_textptr[kTextBufs] = {};
-    DevBuf d_textbuf[kTextBufs], d_tiles, d_tile_off, d_lines, d_lsubj, d_lmeta, d_start, d_first, d_unknown, d_state, d_dict, d_dict2, d_names16, d_arena, d_submap;
+    enum : unsigned char { kBufFree = 0, kBufCopied = 1, kBufScanning = 2, kBufPending = 3 };
+    TextBuf text_buf[kTextBufs];
+    std::mutex copy_mu;   // the text buffers' states and tags (see TextBuf)
+    std::mutex slab_mu;   // a slab is allocated by whoever needs one of its buffers first
+    unsigned long long copy_seq_next = 1;
+    // what kernels write about the blocks copied ahead, in pinned memory, by text buffer: the newlines of a block
+    // counted behind its copy, the inflate kernel's "a member failed" word
+    unsigned long long* copy_newlines = nullptr;   // [kTextBufs], behind the slots of host_back
+    uint32_t* di_any_host = nullptr;               // [kTextBufs], allocated by the first wk_dtok_inflate_ahead
+    DevBuf d_tiles, d_tile_off, d_lines, d_lsubj, d_lmeta, d_start, d_first, d_unknown, d_state, d_dict, d_dict2, d_names16, d_arena, d_submap;
     bool dt_mapped = false;       // the block scanned last has had its lines' ids translated (dtok_submap_kernel)
     bool dt_submap_on = false;    // a map has been given (it may be empty still)
     bool dt_has_excl = false;     // the map holds kLineExcluded: `--exclude` on the device text route
@@ -365,37 +400,17 @@ struct wk_ctx {
     std::vector<ResidentText> resident;
     // gzip members inflated on the device (wk_dinflate.hpp): the compressed bytes, the members' spans, the text and
     // the status words of wk_inflate_members_device
-    DevBuf di_blob, di_meta, di_out, di_status;
-    // ... and of the blocks wk_dtok_inflate_ahead fills, one set per text buffer in use; the kernel's "a member failed"
-    // word of each lands in pinned memory behind the kernel (read by wk_dtok_copy_wait)
-    DevBuf di_comp_k[kTextBufs], di_meta_k[kTextBufs], di_status_k[kTextBufs];
-    uint32_t* di_any_host = nullptr;   // [kTextBufs] pinned
-    bool di_used[kTextBufs] = {};
-    std::vector<int64_t> di_meta_host[kTextBufs];   // what the copies of a block's spans and carry read until they are through
-    std::vector<char> di_carry_host[kTextBufs];
+    DevBuf di_blob, di_meta, di_out, di_status;   // (those of the blocks wk_dtok_inflate_ahead fills: TextBuf)
     const unsigned char* dt_text = nullptr;  // the text of the block scanned last
     int dt_fmt = 0;   // WK_FMT_* of the blocks (wk_dtok_format)
     uint32_t dt_n = 0, dt_lines = 0, dt_dict_mask = 0;
     int32_t dt_dict_names = -1;  // names of the tokenizer the mirror holds
     const wk_tok* dt_dict_tok = nullptr;
     bool dt_ready = false;
-    // the text of a block is copied on a stream of its own into one of two
-    // buffers while the kernels work on the other (wk_dtok_copy)
+    // the text of a block is copied on a stream of its own into a free text buffer while the kernels work on the
+    // buffers of the blocks before it (wk_dtok_copy); its newlines are counted behind the copy on another
     hipStream_t copy_stream = nullptr, count_stream = nullptr;
-    hipEvent_t copy_ev[kTextBufs] = {};
-    const char* copy_src[kTextBufs] = {};
-    DevBuf d_tiles_k[kTextBufs], d_tile_off_k[kTextBufs];          // newlines per tile of a block copied ahead, counted behind its copy
-    unsigned long long* copy_newlines = nullptr;   // [kTextBufs] pinned: their totals
-    bool copy_counted[kTextBufs] = {};
-    uint32_t copy_n[kTextBufs] = {};
-    int dt_cur = 0;
-    // blocks are scanned in the order they were copied: a copy's number tells two buffers with the same tag apart
-    unsigned long long copy_seq[kTextBufs] = {}, copy_seq_next = 1;
-    // a block copied by wk_dtok_copy_ahead: the host bytes are not kept until the scan (the reader reuses its pinned
-    // buffer once the copy is through); what the scan wants from them comes back from the device when it does
-    bool copy_detached[kTextBufs] = {};
-    char copy_last[kTextBufs] = {};   // the block's last byte (a last line without newline)
-    bool dt_detached = false;         // the block scanned last: its host bytes are gone
+    bool dt_detached = false;         // the block scanned last: its host bytes are gone (TextBuf::detached)
     // (wk_dtok_expect) bytes of text the open sample will have brought in all; the records that makes, told from
     // the first block's lines per byte: the sample's record buffers are sized once instead of doubled eight times
     int64_t dt_expect_bytes = 0, w_expect = 0;
@@ -404,14 +419,6 @@ struct wk_ctx {
     // that is under way there, and the scan loop then runs at the pace of the link instead of the kernels'
     unsigned char* host_back = nullptr;   // [kBackSlots][kBackBytes] pinned, then copy_newlines[kTextBufs]
     static constexpr int kBackSlots = 4, kBackBytes = 256;
-    // A text buffer is free, holds a block copied ahead (tagged by copy_src / copy_n), or is the one the
-    // kernels of the block scanned last read (until the next scan begins).  wk_dtok_copy may be called
-    // from another thread than the scans (the host layer's reader thread issues the copies as soon as a
-    // block is cut): the states and tags are guarded by copy_mu.
-    enum : unsigned char { kBufFree = 0, kBufCopied = 1, kBufScanning = 2, kBufPending = 3 };
-    unsigned char buf_state[kTextBufs] = {};
-    std::mutex copy_mu;
-    std::mutex slab_mu;   // a slab is allocated by whoever needs one of its buffers first
     // read maps formatted on the device (wk_readmap.hpp): per job the taxon slot of every subject, the slots' order
     // and shown text; per block the reads' leader lines, line lengths / offsets and the text itself
     struct MapTables {
@@ -496,12 +503,59 @@ hipError_t text_buffer(wk_ctx* c, int k, size_t need) {
             const hipError_t e = slab.reserve(wk_ctx::kTextStride * wk_ctx::kSlabBufs);
             if (e != hipSuccess) return e;
         }
-        c->d_textptr[k] = slab.as<unsigned char>() + (size_t)(k % wk_ctx::kSlabBufs) * wk_ctx::kTextStride;
+        c->text_buf[k].text = slab.as<unsigned char>() + (size_t)(k % wk_ctx::kSlabBufs) * wk_ctx::kTextStride;
         return hipSuccess;
     }
-    const hipError_t e = c->d_textbuf[k].reserve(need);
-    if (e == hipSuccess) c->d_textptr[k] = c->d_textbuf[k].as<unsigned char>();
+    TextBuf& b = c->text_buf[k];
+    const hipError_t e = b.own.reserve(need);
+    if (e == hipSuccess) b.text = b.own.as<unsigned char>();
     return e;
+}
+
+// ---- the searches among the text buffers: each is called with copy_mu held --------------------------------------
+// The oldest block copied ahead with this tag (a reader that reuses its pinned buffers may have copied two blocks of
+// one length from one address); -1: none.
+int textbuf_find_copied(const wk_ctx* c, const char* src, uint32_t n) {
+    int k = -1;
+    for (int q = 0; q < wk_ctx::kTextBufs; ++q) {
+        const TextBuf& b = c->text_buf[q];
+        if (b.state == wk_ctx::kBufCopied && b.src == src && b.n == n && (k < 0 || b.seq < c->text_buf[k].seq)) k = q;
+    }
+    return k;
+}
+
+// Buffer k goes over to `state` and is found by no tag any more.
+void textbuf_claim(wk_ctx* c, int k, unsigned char state) {
+    TextBuf& b = c->text_buf[k];
+    b.state = state;
+    b.src = nullptr;
+    b.counted = false;
+}
+
+// The lowest free buffer, claimed for `state`; -1: none is free.
+int textbuf_take_free(wk_ctx* c, unsigned char state) {
+    for (int q = 0; q < wk_ctx::kTextBufs; ++q)
+        if (c->text_buf[q].state == wk_ctx::kBufFree) {
+            textbuf_claim(c, q, state);
+            c->text_buf[q].detached = false;
+            return q;
+        }
+    return -1;
+}
+
+// The buffer of the block scanned last is free once the next scan begins: its kernels have been waited for.
+void textbuf_release_scanned(wk_ctx* c) {
+    for (TextBuf& b : c->text_buf)
+        if (b.state == wk_ctx::kBufScanning) b.state = wk_ctx::kBufFree;
+}
+
+// Buffer k holds a block copied ahead again (its text is where it was, its newlines count as not counted).
+void textbuf_retag(wk_ctx* c, int k, const char* src, uint32_t n) {
+    TextBuf& b = c->text_buf[k];
+    b.state = wk_ctx::kBufCopied;
+    b.src = src;
+    b.n = n;
+    b.counted = false;
 }
 
 // `bytes` (<= 256, a multiple of 4) from device memory to pinned host memory, by the device itself
@@ -1067,7 +1121,6 @@ int wk_create(int device, wk_ctx** out) {
     // (measurement: WOLTKA_NO_FUSED=1 keeps every block of the text route on the six kernels of wk_dtok.hpp, for
     // whole `woltka classify` calls that cannot reach wk_tune)
     if (const char* nf = getenv("WOLTKA_NO_FUSED")) c->use_fused = (nf[0] && nf[0] != '0') ? 0 : 1;
-    if (const char* nc = getenv("WOLTKA_FZ_NO_CHAIN")) c->fz_no_chain = nc[0] && nc[0] != '0';
     if (const char* nl = getenv("WOLTKA_NO_LAG")) c->lag_enabled = !(nl[0] && nl[0] != '0');
     if (const char* lp = getenv("WOLTKA_LAG_POLL")) c->lag_poll = lp[0] && lp[0] != '0';
     if (const char* sm = getenv("WOLTKA_STRIPES_MIN"))
@@ -1096,15 +1149,12 @@ void wk_destroy(wk_ctx* c) {
     c->w_backup3.release();
     for (hipEvent_t& e : c->lag_ev)
         if (e) (void)hipEventDestroy(e);
-    for (int q = 0; q < wk_ctx::kTextBufs; ++q) {
-        c->d_tiles_k[q].release();
-        c->d_tile_off_k[q].release();
-        c->di_comp_k[q].release();
-        c->di_meta_k[q].release();
-        c->di_status_k[q].release();
-        c->d_textbuf[q].release();
-        if (q % wk_ctx::kSlabBufs == 0) c->d_textslab[q / wk_ctx::kSlabBufs].release();
+    for (TextBuf& b : c->text_buf) {
+        for (DevBuf* d : {&b.tiles, &b.tile_off, &b.di_comp, &b.di_meta, &b.di_status, &b.own}) d->release();
+        for (hipEvent_t ev : {b.ev, b.ev0, b.evm})
+            if (ev) (void)hipEventDestroy(ev);
     }
+    for (DevBuf& slab : c->d_textslab) slab.release();
     for (DevBuf* b : {&c->d_tiles, &c->d_tile_off, &c->d_lines, &c->d_lsubj, &c->d_lmeta, &c->d_start, &c->d_first, &c->d_unknown, &c->d_lbeg, &c->d_lend, &c->d_llen, &c->d_lscan, &c->d_gmap,
                       &c->d_state, &c->d_dict, &c->d_dict2, &c->d_names16, &c->d_arena, &c->d_submap, &c->cv_key[0], &c->cv_key[1], &c->cv_end[0], &c->cv_end[1],
                       &c->cv_reach, &c->cv_hist, &c->cv_tiles, &c->cv_tile_off, &c->cv_state, &c->cv_stage[0], &c->cv_stage[1], &c->cv_stage[2],
@@ -1119,12 +1169,6 @@ void wk_destroy(wk_ctx* c) {
     if (c->host_back) (void)hipHostFree(c->host_back);
     for (const wk_ctx::HostReg& r : c->regs) (void)hipHostUnregister(const_cast<char*>(r.p));
     c->regs.clear();
-    for (hipEvent_t ev : c->copy_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : c->copy_ev0)
-        if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : c->copy_evm)
-        if (ev) (void)hipEventDestroy(ev);
     if (c->di_any_host) (void)hipHostFree(c->di_any_host);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->count_stream) (void)hipStreamDestroy(c->count_stream);
@@ -3067,9 +3111,15 @@ static DtokArgs dtok_args(wk_ctx* c) {
     return a;
 }
 
-// Start copying text[begin, stop) of a block to the device on the copy stream;
-// the wk_dtok_scan of the same block finds it there.  At most one block ahead of
-// the one being scanned (two buffers).
+// Newlines of text[0, n) per tile of kDtokTile bytes into tiles[], their exclusive prefix sums into tile_off[], the
+// total to *total (device or pinned memory) -- queued on `stream`.  The count zeroes the 64 bytes of pad behind the text.
+static void count_newlines(const unsigned char* text, uint32_t n, unsigned long long* tiles, unsigned long long* tile_off,
+                           unsigned long long* total, hipStream_t stream) {
+    const uint32_t n_tiles = (n + kDtokTile - 1) / kDtokTile;
+    hipLaunchKernelGGL(dtok_count_kernel, dim3(n_tiles), dim3(kDtokThreads), 0, stream, text, n, tiles);
+    hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, stream, tiles, tile_off, (int64_t)n_tiles, total);
+}
+
 // hipMemcpyAsync host -> device of [src, src + n), cut where registered ranges
 // (wk_host_register) begin and end: one copy may not span two registrations.
 static hipError_t copy_text_async(wk_ctx* c, void* dst, const char* src, size_t n, hipStream_t stream) {
@@ -3144,15 +3194,11 @@ static int dtok_copy_impl(wk_ctx* c, const char* text, int64_t begin, int64_t st
         std::lock_guard<std::mutex> lock(c->copy_mu);
         if (!c->copy_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
         if (!c->count_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->count_stream, hipStreamNonBlocking));
-        for (int q = 0; q < wk_ctx::kTextBufs && k < 0; ++q)
-            if (c->buf_state[q] == wk_ctx::kBufFree) k = q;
-        if (k >= 0) {
-            c->buf_state[k] = wk_ctx::kBufCopied;
-            c->copy_src[k] = nullptr;  // (tagged below, once the copy is queued)
-            c->copy_seq[k] = c->copy_seq_next++;
-        }
+        k = textbuf_take_free(c, wk_ctx::kBufCopied);  // (tagged below, once the copy is queued)
+        if (k >= 0) c->text_buf[k].seq = c->copy_seq_next++;
     }
     if (k < 0) return fail(c, WK_E_STATE, "more than %d blocks copied ahead of the scan", wk_ctx::kTextBufs - 1);
+    TextBuf& b = c->text_buf[k];
     auto lap_mark = [&](int i) {
         const auto now = std::chrono::steady_clock::now();
         const double dt = std::chrono::duration<double>(now - lap_t).count();
@@ -3160,73 +3206,72 @@ static int dtok_copy_impl(wk_ctx* c, const char* text, int64_t begin, int64_t st
         if (i == 1) c->lap_c[4] = std::max(c->lap_c[4], dt);
         lap_t = now;
     };
-    if (!c->copy_ev[k]) HIP_TRY(c, hipEventCreate(&c->copy_ev[k]));
-    if (!c->copy_ev0[k]) HIP_TRY(c, hipEventCreate(&c->copy_ev0[k]));
-    if (!c->copy_evm[k]) HIP_TRY(c, hipEventCreate(&c->copy_evm[k]));
+    if (!b.ev) HIP_TRY(c, hipEventCreate(&b.ev));
+    if (!b.ev0) HIP_TRY(c, hipEventCreate(&b.ev0));
+    if (!b.evm) HIP_TRY(c, hipEventCreate(&b.evm));
     const uint32_t n = (uint32_t)n64;
     // (at least a full block's worth from the start: a file's first blocks are small, and growing a buffer
     // three times means three hipFree / hipMalloc pairs per buffer while the dictionary is cold)
     lap_mark(0);
     HIP_TRY(c, text_buffer(c, k, (inf ? (size_t)(inf->n_carry + inf->off[inf->n_members]) : (size_t)n) + 64));
     lap_mark(1);
-    HIP_TRY(c, hipEventRecord(c->copy_ev0[k], c->copy_stream));
-    c->di_used[k] = inf != nullptr;
+    HIP_TRY(c, hipEventRecord(b.ev0, c->copy_stream));
+    b.di_used = inf != nullptr;
     if (inf) {
         // the carry, then the members' text behind it: compressed bytes and spans in, one launch of the inflate
         // kernel, its failure word out to pinned memory -- all on the copy stream, so the scan of the block before
         // goes on meanwhile.  (Spans and carry are the caller's for this call only: the copies read this buffer's own.)
         const int64_t nm = inf->n_members;
         if (!c->di_any_host) HIP_TRY(c, hipHostMalloc((void**)&c->di_any_host, sizeof(uint32_t) * wk_ctx::kTextBufs, hipHostMallocDefault));
-        HIP_TRY(c, c->di_comp_k[k].reserve((size_t)inf->n_comp));
-        HIP_TRY(c, c->di_meta_k[k].reserve((size_t)(3 * nm + 1) * 8));
-        HIP_TRY(c, c->di_status_k[k].reserve((size_t)(nm + 2) * 4));
-        std::vector<int64_t>& meta = c->di_meta_host[k];
+        HIP_TRY(c, b.di_comp.reserve((size_t)inf->n_comp));
+        HIP_TRY(c, b.di_meta.reserve((size_t)(3 * nm + 1) * 8));
+        HIP_TRY(c, b.di_status.reserve((size_t)(nm + 2) * 4));
+        std::vector<int64_t>& meta = b.di_meta_host;
         meta.resize((size_t)(3 * nm + 1));
         std::copy(inf->lo, inf->lo + nm, meta.begin());
         std::copy(inf->hi, inf->hi + nm, meta.begin() + nm);
         for (int64_t i = 0; i <= nm; ++i) meta[(size_t)(2 * nm + i)] = inf->off[i] + inf->n_carry;
-        c->di_carry_host[k].assign(inf->carry, inf->carry + inf->n_carry);
-        int64_t* d_meta = c->di_meta_k[k].as<int64_t>();
+        b.di_carry_host.assign(inf->carry, inf->carry + inf->n_carry);
+        int64_t* d_meta = b.di_meta.as<int64_t>();
         c->di_any_host[k] = 0;
         if (inf->n_carry)
-            HIP_TRY(c, hipMemcpyAsync(c->d_textptr[k], c->di_carry_host[k].data(), (size_t)inf->n_carry, hipMemcpyHostToDevice, c->copy_stream));
-        HIP_TRY(c, hipMemcpyAsync(c->di_comp_k[k].p, text, (size_t)inf->n_comp, hipMemcpyHostToDevice, c->copy_stream));
+            HIP_TRY(c, hipMemcpyAsync(b.text, b.di_carry_host.data(), (size_t)inf->n_carry, hipMemcpyHostToDevice, c->copy_stream));
+        HIP_TRY(c, hipMemcpyAsync(b.di_comp.p, text, (size_t)inf->n_comp, hipMemcpyHostToDevice, c->copy_stream));
         HIP_TRY(c, hipMemcpyAsync(d_meta, meta.data(), meta.size() * 8, hipMemcpyHostToDevice, c->copy_stream));
-        HIP_TRY(c, hipMemsetAsync(c->di_status_k[k].p, 0, (size_t)(nm + 2) * 4, c->copy_stream));
-        dinf_launch(c, c->di_comp_k[k].as<unsigned char>(), d_meta, nm, c->d_textptr[k], c->di_status_k[k].as<uint32_t>(), c->copy_stream);
+        HIP_TRY(c, hipMemsetAsync(b.di_status.p, 0, (size_t)(nm + 2) * 4, c->copy_stream));
+        dinf_launch(c, b.di_comp.as<unsigned char>(), d_meta, nm, b.text, b.di_status.as<uint32_t>(), c->copy_stream);
         HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemcpyAsync(&c->di_any_host[k], c->di_status_k[k].as<uint32_t>() + nm, 4, hipMemcpyDeviceToHost, c->copy_stream));
+        HIP_TRY(c, hipMemcpyAsync(&c->di_any_host[k], b.di_status.as<uint32_t>() + nm, 4, hipMemcpyDeviceToHost, c->copy_stream));
     } else {
-        // (only the copy on this stream: the 64 zero bytes behind the text are a fill
-        // kernel, which wk_dtok_scan launches on its own stream behind the copy's event)
-        HIP_TRY(c, copy_text_async(c, c->d_textptr[k], text + begin, (size_t)n, c->copy_stream));
+        // (only the copy on this stream: the 64 zero bytes behind the text are written by the newline count,
+        // which runs on another stream behind the copy's event -- here or in the scan)
+        HIP_TRY(c, copy_text_async(c, b.text, text + begin, (size_t)n, c->copy_stream));
     }
-    HIP_TRY(c, hipEventRecord(c->copy_evm[k], c->copy_stream));
+    HIP_TRY(c, hipEventRecord(b.evm, c->copy_stream));
     lap_mark(2);
     // ... and, behind the copy, the count of the block's newlines -- on a stream of its own, so that the next
     // block's copy follows this one without a gap; the total lands in pinned memory (written by the kernel: no
     // trip through the DMA queue): wk_dtok_scan finds the number on the host instead of waiting for it
-    HIP_TRY(c, hipStreamWaitEvent(c->count_stream, c->copy_evm[k], 0));
-    c->copy_counted[k] = false;
+    HIP_TRY(c, hipStreamWaitEvent(c->count_stream, b.evm, 0));
+    b.counted = false;
     if (!c->fused_streak && c->count_ahead) {  // (blocks that go through the one kernel need no count: wk_dtok_fused.hpp)
         const uint32_t n_tiles = (n + kDtokTile - 1) / kDtokTile;
-        HIP_TRY(c, c->d_tiles_k[k].reserve((size_t)n_tiles * 8));
-        HIP_TRY(c, c->d_tile_off_k[k].reserve((size_t)n_tiles * 8));
-        hipLaunchKernelGGL(dtok_count_kernel, dim3(n_tiles), dim3(kDtokThreads), 0, c->count_stream, c->d_textptr[k], n,
-                           c->d_tiles_k[k].as<unsigned long long>());
-        hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, c->count_stream, c->d_tiles_k[k].as<unsigned long long>(),
-                           c->d_tile_off_k[k].as<unsigned long long>(), (int64_t)n_tiles, &c->copy_newlines[k]);
+        HIP_TRY(c, b.tiles.reserve((size_t)n_tiles * 8));
+        HIP_TRY(c, b.tile_off.reserve((size_t)n_tiles * 8));
+        count_newlines(b.text, n, b.tiles.as<unsigned long long>(), b.tile_off.as<unsigned long long>(), &c->copy_newlines[k],
+                       c->count_stream);
         HIP_TRY(c, hipGetLastError());
-        c->copy_counted[k] = true;
+        b.counted = true;
     }
-    HIP_TRY(c, hipEventRecord(c->copy_ev[k], c->count_stream));
+    HIP_TRY(c, hipEventRecord(b.ev, c->count_stream));
     lap_mark(3);
     {
+        // (the tag last: from here on a scan finds the block, on whatever thread it runs)
         std::lock_guard<std::mutex> lock(c->copy_mu);
-        c->copy_n[k] = n;
-        c->copy_last[k] = inf ? inf->last : text[stop - 1];
-        c->copy_detached[k] = detached;
-        c->copy_src[k] = text + begin;
+        b.n = n;
+        b.last = inf ? inf->last : text[stop - 1];
+        b.detached = detached;
+        b.src = text + begin;
     }
     if (ticket) *ticket = k;
     return WK_OK;
@@ -3249,10 +3294,10 @@ int wk_dtok_copy_ahead(wk_ctx* c, const char* text, int64_t begin, int64_t stop,
 int wk_dtok_copy_wait(wk_ctx* c, int32_t ticket) {
     if (!c) return WK_E_ARG;
     if (ticket < 0) return WK_OK;  // (an empty block: nothing was copied)
-    if (ticket >= wk_ctx::kTextBufs || !c->copy_evm[ticket]) return fail(c, WK_E_ARG, "not a ticket of wk_dtok_copy_ahead");
+    if (ticket >= wk_ctx::kTextBufs || !c->text_buf[ticket].evm) return fail(c, WK_E_ARG, "not a ticket of wk_dtok_copy_ahead");
     DeviceGuard guard(c->device);
-    HIP_TRY(c, hipEventSynchronize(c->copy_evm[ticket]));
-    if (c->di_used[ticket] && c->di_any_host && c->di_any_host[ticket])
+    HIP_TRY(c, hipEventSynchronize(c->text_buf[ticket].evm));
+    if (c->text_buf[ticket].di_used && c->di_any_host && c->di_any_host[ticket])
         return fail(c, WK_E_STATE, "gzip member: one of the block does not inflate to what its trailer says (stream, size, CRC-32)");
     return WK_OK;
 }
@@ -3290,17 +3335,10 @@ int wk_dtok_copy_drop(wk_ctx* c) {
     if (c->count_stream) HIP_TRY(c, hipStreamSynchronize(c->count_stream));
     std::lock_guard<std::mutex> lock(c->copy_mu);
     for (int q = 0; q < wk_ctx::kTextBufs; ++q)
-        if (c->buf_state[q] == wk_ctx::kBufCopied) {
-            c->buf_state[q] = wk_ctx::kBufFree;
-            c->copy_src[q] = nullptr;
-            c->copy_counted[q] = false;
-        }
-    for (int q = 0; q < wk_ctx::kTextBufs; ++q)
-        if (c->buf_state[q] == wk_ctx::kBufFree) {   // (compressed bytes of blocks long scanned)
-            c->di_comp_k[q].release();
-            c->di_meta_k[q].release();
-            c->di_status_k[q].release();
-        }
+        if (c->text_buf[q].state == wk_ctx::kBufCopied) textbuf_claim(c, q, wk_ctx::kBufFree);
+    for (TextBuf& b : c->text_buf)
+        if (b.state == wk_ctx::kBufFree)   // (compressed bytes of blocks long scanned)
+            for (DevBuf* d : {&b.di_comp, &b.di_meta, &b.di_status}) d->release();
     // (the slabs a reader far ahead of the scans took -- up to 12 GB -- go back to the device once none of their
     // buffers is in use: what follows the file, count tables and records, must not compete with parked text.
     // The first slab stays: a reader that keeps close to the scans lives in it)
@@ -3309,13 +3347,13 @@ int wk_dtok_copy_drop(wk_ctx* c) {
         for (int sl = 1; sl < wk_ctx::kTextBufs / wk_ctx::kSlabBufs; ++sl) {
             if (!c->d_textslab[sl].p) continue;
             bool idle = true;
-            for (int q = sl * wk_ctx::kSlabBufs; q < (sl + 1) * wk_ctx::kSlabBufs; ++q) idle = idle && c->buf_state[q] == wk_ctx::kBufFree;
+            for (int q = sl * wk_ctx::kSlabBufs; q < (sl + 1) * wk_ctx::kSlabBufs; ++q) idle = idle && c->text_buf[q].state == wk_ctx::kBufFree;
             if (!idle) continue;
             HIP_TRY(c, hipStreamSynchronize(c->stream));  // (the scan of a block that lived there)
             for (int q = sl * wk_ctx::kSlabBufs; q < (sl + 1) * wk_ctx::kSlabBufs; ++q)
-                if (c->d_textptr[q] >= c->d_textslab[sl].as<unsigned char>() &&
-                    c->d_textptr[q] < c->d_textslab[sl].as<unsigned char>() + wk_ctx::kTextStride * wk_ctx::kSlabBufs)
-                    c->d_textptr[q] = nullptr;
+                if (c->text_buf[q].text >= c->d_textslab[sl].as<unsigned char>() &&
+                    c->text_buf[q].text < c->d_textslab[sl].as<unsigned char>() + wk_ctx::kTextStride * wk_ctx::kSlabBufs)
+                    c->text_buf[q].text = nullptr;
             if (c->dt_text >= c->d_textslab[sl].as<unsigned char>() && c->dt_text < c->d_textslab[sl].as<unsigned char>() + c->d_textslab[sl].cap)
                 c->dt_text = nullptr;  // (wk_dtok_text_back of that block: refused from now on)
             c->d_textslab[sl].release();
@@ -3427,10 +3465,7 @@ int wk_text_upload(wk_ctx* c, const char* text, int64_t begin, int64_t stop) {
     HIP_TRY(c, hipMalloc(&off, (size_t)n_tiles * 8));
     HIP_TRY(c, hipMemcpyAsync(dev, r.host, n, hipMemcpyHostToDevice, c->stream));
     // (the pad behind the text: dtok_count_kernel's last tile; the total: tile_scan_kernel stores it)
-    hipLaunchKernelGGL(dtok_count_kernel, dim3(n_tiles), dim3(kDtokThreads), 0, c->stream, (const unsigned char*)dev, n,
-                       (unsigned long long*)tiles);
-    hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, c->stream, (const unsigned long long*)tiles, (unsigned long long*)off,
-                       (int64_t)n_tiles, scalar_u64(c, 3));
+    count_newlines((const unsigned char*)dev, n, (unsigned long long*)tiles, (unsigned long long*)off, scalar_u64(c, 3), c->stream);
     HIP_TRY(c, hipMemcpyAsync(&r.n_newlines, scalar_u64(c, 3), 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     (void)hipFree(tiles);
@@ -3543,12 +3578,6 @@ int wk_dtok_format(wk_ctx* c, int fmt) {
     return WK_OK;
 }
 
-// a block the one kernel handed back: see dtok_scan_impl
-static void fz_handed_back(wk_ctx* c) {
-    c->fz_back_streak = std::min(c->fz_back_streak + 1, 6);
-    if (c->fz_back_streak >= 2) c->fz_skip = 1 << (c->fz_back_streak - 1);
-}
-
 static DevBuf& fz_bk(wk_ctx* c, int i) { return i == 0 ? c->w_backup : i == 1 ? c->w_backup2 : c->w_backup3; }
 
 // The one-kernel tokenizer's geometry for a block of n bytes: one contiguous span per persistent workgroup
@@ -3566,321 +3595,411 @@ static int dtok_emit_launch(wk_ctx* c, bool* ordered_out, unsigned long long* to
 static int dtok_emit_finish(wk_ctx* c, bool keep, bool ordered, DtokState st, unsigned long long totals, int64_t* n_reads,
                             int64_t* n_records);
 
-// `emit` (may be null): with the words of this sample open (wk_words_begin), the emission is queued right behind the
-// parse — the usual block brings no subject the dictionary does not know — and the host waits once for both; *emit = 1
-// when the block's records have been appended that way (then emitted[0..1] = reads, records).
-static int dtok_scan_impl(wk_ctx* c, wk_tok* tok, const char* text, int64_t begin, int64_t stop, int extra, int64_t* n_lines, int* status,
-                          int* emit, int64_t* emitted) {
-    if (!c || !tok || !text || begin < 0 || stop < begin || !n_lines || !status) return WK_E_ARG;
-    if (emit) *emit = 0;
-    if (c->lag_count) return fail(c, WK_E_STATE, "blocks whose verdict has not been read (wk_dtok_scan_emit_end)");
-    Lap lap(&c->lap_s[1]);
-    *status = 1;
-    *n_lines = 0;
+// (measurement) The block as wk_text_upload left it on the device; null: it is not resident.
+static const wk_ctx::ResidentText* resident_text(const wk_ctx* c, const char* src, uint32_t n) {
+    const wk_ctx::ResidentText* res = nullptr;
+    for (const wk_ctx::ResidentText& r : c->resident)
+        if (r.host == src && r.n == n) res = &r;
+    return res;
+}
+
+// The block's scalars and its list of subjects the dictionary does not hold.
+static hipError_t dtok_scratch_reserve(wk_ctx* c) {
+    const hipError_t e = c->d_state.reserve(sizeof(DtokState) + 64);
+    return e != hipSuccess ? e : c->d_unknown.reserve((size_t)(1 << 20) * 8);
+}
+
+// (wk_dtok_expect) The records that the open sample's text will make, told from the lines per byte of the block
+// scanned last, its first: a record per line at most; 8 % on top of the block's rate, never more than the 2^30 a pass
+// holds.  words_room sizes the sample's record buffers from it.
+static void words_expect_from_block(wk_ctx* c) {
+    if (c->dt_expect_bytes <= 0 || c->w_expect != 0 || c->dt_n == 0) return;
+    const double lines = (double)c->dt_expect_bytes * ((double)c->dt_lines / (double)c->dt_n) * 1.08 + (double)c->dt_lines;
+    c->w_expect = (int64_t)std::min(lines, (double)(1ll << 30));
+}
+
+// ---- the one-kernel tokenizer (wk_dtok_fused.hpp) -----------------------------------------------------------------
+// The usual block of a sample whose words are open -- SAM text, records for the weighted histogram, every subject
+// known -- goes through ONE kernel.  A block it hands back (a subject the dictionary does not hold, a line for the
+// host tokenizer, a run or a line beyond its window) leaves the streams as they were and takes the six kernels.
+// This is what wk_dtok_scan_emit and wk_dtok_scan_emit_begin both ask of a block before they try the kernel; each adds
+// its own: the flavour and `fz_skip`, which only the former counts down, there, the blocks under way here.
+static bool fused_eligible(const wk_ctx* c, const wk_tok* tok) {
+    return c->use_fused && c->dt_fmt == WK_FMT_SAM && c->w_open && c->w_mode == 0 && !c->dt_keep_reads &&
+           wkx_tok_n_names(tok) < (1 << 23) - 1;
+}
+
+// Queue the kernel for the block of n bytes at `text`, its records to `streams` (at most kFzStreams of them).
+// ONE launch per block while blocks follow one another through this kernel: its last workgroup leaves the cursors as
+// they are behind the block in the next of three buffers -- the next block's "before" --, the block's scalars in
+// pinned memory and cleared ones on the device.  fz_bk(ring) is this block's "before"; anything else that has moved
+// the cursors or the scalars since the last launch has broken the chain (`fz_chain`): the small kernel in front, then.
+// The scalars land in slot `host_slot` of the pinned scratch and, with seq != 0, that number 128 bytes into the slot
+// once they are there.  Every field of FusedArgs is set here and nowhere else.
+static int fused_launch(wk_ctx* c, const StreamSet& streams, const unsigned char* text, uint32_t n, bool open_end, int ring, int host_slot,
+                        uint32_t seq) {
+    static_assert(sizeof(DtokState) <= 128 && wk_ctx::kBackBytes >= 132, "the slot's second half holds the block's sequence number");
+    FusedArgs fa{};
+    const unsigned grid = fused_spans(c, n, &fa.span);
+    if (fa.span % 16u) return fail(c, WK_E_ARG, "spans of the one-kernel tokenizer are multiples of 16 bytes");
+    HIP_TRY(c, dtok_scratch_reserve(c));
+    for (int i = 0; i < 3; ++i) HIP_TRY(c, fz_bk(c, i).reserve(kMaxStreams * 8));
+    fa.text = text;
+    fa.n = n;
+    fa.open_end = open_end ? 1u : 0u;
+    fa.dict8 = c->d_dict2.as<DictSlot8>();
+    fa.names16 = c->d_names16.as<uint4>();
+    fa.dict_mask = c->dt_dict_mask;
+    fa.arena = c->d_arena.as<unsigned char>();
+    fa.unknown = c->d_unknown.as<uint2>();
+    fa.unknown_cap = (uint32_t)(c->d_unknown.cap / 8);
+    fa.state = c->d_state.as<DtokState>();
+    unsigned char* slot = c->host_back + (size_t)host_slot * wk_ctx::kBackBytes;
+    fa.host_state = reinterpret_cast<DtokState*>(slot);
+    fa.backup_prev = fz_bk(c, ring).as<unsigned long long>();   // (the block's records: the cursors' advance over it)
+    fa.backup_next = fz_bk(c, (ring + 1) % 3).as<unsigned long long>();
+    fa.host_seq = seq ? reinterpret_cast<uint32_t*>(slot + 128) : nullptr;
+    fa.seq = seq;
+    fa.streams = streams;
+    fa.submap = c->dt_submap_on ? c->d_submap.as<int32_t>() : nullptr;
+    fa.n_submap = c->dt_submap_n;
+    fa.ablate = c->fused_ablate;
+    c->w_counts_known = false;
+    KernelTimer* kf = ktimer_begin(c, "dtok_fused");
+    if (!c->fz_chain)
+        hipLaunchKernelGGL(dtok_fused_begin_kernel, dim3(1), dim3(64), 0, c->stream, fz_bk(c, ring).as<unsigned long long>(),
+                           (const unsigned long long*)streams.cursor, fa.state);
+    hipLaunchKernelGGL(dtok_fused_kernel, dim3(grid), dim3(kFzThreads), 0, c->stream, fa);
+    ktimer_end(c, kf);
+    HIP_TRY(c, hipGetLastError());
+    return WK_OK;
+}
+
+// The kernel kept a block of n bytes (`st`: its scalars; its records have been accepted).  Returns the block's lines.
+static uint32_t fz_kept(wk_ctx* c, const DtokState& st, uint32_t n, bool open_end) {
+    const uint32_t lines = (uint32_t)st.n_lines + (open_end ? 1u : 0u);
+    c->dt_lines = lines;
+    c->dt_lpb = (double)lines / (double)n;
+    c->fused_streak = true;
+    c->fz_back_streak = 0;
+    ++c->fused_blocks;
+    return lines;
+}
+
+// The kernel handed a block back (the cursors have been put back: the next launch seeds its "before" again).
+static void fz_handed_back(wk_ctx* c) {
+    c->fused_streak = false;
+    c->fz_chain = false;
+    ++c->fused_fallbacks;
+    // (text the one kernel keeps handing back -- runs longer than its window, say -- pays for both ways block after
+    // block: after two blocks in a row it is left out for 2, 4, ... 32 blocks before it is tried again)
+    c->fz_back_streak = std::min(c->fz_back_streak + 1, 6);
+    if (c->fz_back_streak >= 2) c->fz_skip = 1 << (c->fz_back_streak - 1);
+}
+
+// ---- wk_dtok_scan / wk_dtok_scan_emit: one block, step by step ------------------------------------------------
+// The block on its way through dtok_scan_impl.
+struct ScanBlock {
+    wk_tok* tok;
+    const char* src;        // the host's bytes: the block's tag, and its text unless c->dt_detached
+    uint32_t n;
+    bool extra;             // the "ex" flavour
+    int64_t* n_lines;       // the caller's
+    int* status;
+    int* emit;
+    int64_t* emitted;
+    // where the text was found (the device pointer is c->dt_text)
+    enum { kResident, kCopiedAhead, kCopiedNow } where;
+    const wk_ctx::ResidentText* res;   // kResident
+    int k;                             // otherwise: the text buffer
+    bool counted;           // kCopiedAhead: the newlines were counted behind the copy
+    bool open_end;          // a last line without newline
+    bool fuse;              // the block tries the one kernel
+    bool have_count;        // n_newlines and tile_off are there
+    unsigned long long n_newlines;
+    const unsigned long long* tile_off;
+    uint32_t lines;         // counted, or (!have_count) what the block has at most
+    KernelTimer* kt;        // the open bracket of family "dtok_lines"
+    std::chrono::steady_clock::time_point lap_t;
+};
+
+static void scan_lap(wk_ctx* c, ScanBlock& s, int i) {
+    const auto now = std::chrono::steady_clock::now();
+    c->lap_x[i] += std::chrono::duration<double>(now - s.lap_t).count();
+    s.lap_t = now;
+}
+
+// The block's records have been appended: what wk_dtok_scan_emit tells its caller then.
+static void scan_reply_emitted(wk_ctx* c, const ScanBlock& s, int64_t n_reads, int64_t n_records) {
+    *s.status = 0;
+    *s.n_lines = s.lines;
+    *s.emit = 1;
+    s.emitted[0] = n_reads;
+    s.emitted[1] = n_records;
+    c->dt_ready = false;  // (nothing left for wk_dtok_emit)
+}
+
+// A block that has not been counted has no more lines than bytes / 7 -- a mapped record is "q\tf\tr\t\n" at least --
+// and, once the sample has shown its lines per byte, a quarter more than that; the kernel reports records that find
+// no room.
+static uint32_t lines_at_most(const wk_ctx* c, uint32_t n) {
+    double est = (double)n / 7.0 + 1.0;
+    if (c->dt_lpb > 0.0) est = std::min(est, (double)n * c->dt_lpb * 1.25 + 65536.0);
+    return (uint32_t)est;
+}
+
+// Is the block the device's at all?  (false: *status stays 1, the host tokenizer takes it)
+static bool scan_checks(wk_ctx* c, ScanBlock& s, int64_t n64) {
+    *s.status = 1;
+    *s.n_lines = 0;
     c->dt_ready = false;
-    c->dt_extra = extra != 0;
+    c->dt_extra = s.extra;
     c->cv_line_next = 0;
     c->dx_looked = false;
     c->dx_runs = false;
     // (an exclusion set: the plain flavour takes it as kLineExcluded entries of the subject map, wk_dtok_subject_map;
     // the "ex" parsers' way with it -- align.py:481-547 yields a stale pool at the end of a file -- stays the host's)
-    if (!wkx_tok_device_ok(tok) && (extra || !c->dt_submap_on)) return WK_OK;
-    if (extra && c->dt_fmt == WK_FMT_MAP) return WK_OK;  // (a simple map has no "ex" flavour, align.py:236)
-    const int64_t n64 = stop - begin;
-    if (n64 >= (1ll << 31) - 64) return WK_OK;
-    DeviceGuard guard(c->device);
-    KtScope kt_scope(c);
-    const uint32_t n = (uint32_t)n64;
-    c->dt_n = n;
-    c->dt_lines = 0;
-    if (n == 0) {
-        *status = 0;
-        c->dt_ready = true;
-        return WK_OK;
-    }
-    const char* src = text + begin;
-    // the block's text: copied ahead by wk_dtok_copy (then the kernels only wait
-    // for that copy), or copied now
-    int k = -1;
-    const unsigned char* resident = nullptr;
-    const wk_ctx::ResidentText* res = nullptr;
-    for (const wk_ctx::ResidentText& r : c->resident)
-        if (r.host == src && r.n == n) {
-            resident = r.dev;
-            res = &r;
-        }
-    bool counted = false, counted_or_ahead = false;
-    auto lap_t = std::chrono::steady_clock::now();
-    auto lap_mark = [&](int i) {
-        const auto now = std::chrono::steady_clock::now();
-        c->lap_x[i] += std::chrono::duration<double>(now - lap_t).count();
-        lap_t = now;
-    };
+    if (!wkx_tok_device_ok(s.tok) && (s.extra || !c->dt_submap_on)) return false;
+    if (s.extra && c->dt_fmt == WK_FMT_MAP) return false;  // (a simple map has no "ex" flavour, align.py:236)
+    if (n64 >= (1ll << 31) - 64) return false;
+    s.n = (uint32_t)n64;
+    return true;
+}
+
+// The block's text: resident (measurement), copied ahead by wk_dtok_copy (then the kernels only wait for that copy),
+// or copied now.
+static int scan_locate_text(wk_ctx* c, ScanBlock& s) {
+    s.res = resident_text(c, s.src, s.n);
+    s.where = ScanBlock::kResident;
+    s.k = -1;
+    s.lap_t = std::chrono::steady_clock::now();
     {
         std::lock_guard<std::mutex> lock(c->copy_mu);
-        // (the buffer of the block scanned before is free from here on: its kernels have been waited for)
-        for (int q = 0; q < wk_ctx::kTextBufs; ++q)
-            if (c->buf_state[q] == wk_ctx::kBufScanning) c->buf_state[q] = wk_ctx::kBufFree;
-        // (the oldest copy with this tag: a reader that reuses its pinned buffers may have copied two blocks
-        // of one length from one address)
-        for (int q = 0; q < wk_ctx::kTextBufs && !resident; ++q)
-            if (c->buf_state[q] == wk_ctx::kBufCopied && c->copy_src[q] == src && c->copy_n[q] == n &&
-                (k < 0 || c->copy_seq[q] < c->copy_seq[k]))
-                k = q;
-        if (!resident && k < 0) {  // not copied ahead: a free buffer, copied into below
-            for (int q = 0; q < wk_ctx::kTextBufs && k < 0; ++q)
-                if (c->buf_state[q] == wk_ctx::kBufFree) k = q;
-            if (k < 0) return fail(c, WK_E_STATE, "every text buffer holds a block copied ahead");
-            c->copy_counted[k] = false;
-            c->copy_src[k] = nullptr;
-            c->copy_detached[k] = false;
-            k = -1 - k;  // (marks "copy now")
-        } else if (!resident) {
-            counted = c->copy_counted[k];
-            counted_or_ahead = true;
-        }
-        c->dt_detached = !resident && k >= 0 && c->copy_detached[k];
-        if (!resident) {
-            const int kk = k >= 0 ? k : -1 - k;
-            c->buf_state[kk] = wk_ctx::kBufScanning;
-            c->copy_src[kk] = nullptr;  // (the buffer's tag is used up)
-            c->copy_counted[kk] = false;
+        textbuf_release_scanned(c);
+        c->dt_detached = false;
+        if (!s.res && (s.k = textbuf_find_copied(c, s.src, s.n)) >= 0) {
+            s.where = ScanBlock::kCopiedAhead;
+            s.counted = c->text_buf[s.k].counted;
+            c->dt_detached = c->text_buf[s.k].detached;
+            textbuf_claim(c, s.k, wk_ctx::kBufScanning);   // (the buffer's tag is used up)
+        } else if (!s.res) {
+            s.where = ScanBlock::kCopiedNow;
+            if ((s.k = textbuf_take_free(c, wk_ctx::kBufScanning)) < 0) return fail(c, WK_E_STATE, "every text buffer holds a block copied ahead");
         }
     }
-    if (resident) {
-        // (measurement: the block is on the device already, 64 zero bytes behind it)
-    } else if (k >= 0) {
-        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->copy_ev[k], 0));  // (the pad: zeroed by the count behind the copy)
+    if (s.where == ScanBlock::kResident) {
+        c->dt_text = s.res->dev;   // (64 zero bytes behind it)
     } else {
-        k = -1 - k;
-        HIP_TRY(c, text_buffer(c, k, (size_t)n + 64));
-        HIP_TRY(c, copy_text_async(c, c->d_textptr[k], src, n, c->stream));  // (the pad: zeroed by the count below)
+        TextBuf& b = c->text_buf[s.k];
+        if (s.where == ScanBlock::kCopiedAhead) {
+            HIP_TRY(c, hipStreamWaitEvent(c->stream, b.ev, 0));  // (the pad: zeroed by the count behind the copy)
+        } else {
+            HIP_TRY(c, text_buffer(c, s.k, (size_t)s.n + 64));
+            HIP_TRY(c, copy_text_async(c, b.text, s.src, s.n, c->stream));  // (the pad: zeroed by the count below)
+        }
+        c->dt_text = b.text;
     }
-    if (!resident) c->dt_cur = k;
-    lap_mark(0);
-    c->dt_text = resident ? resident : c->d_textptr[k];
-    // line starts: newlines per tile -> offsets -> positions
-    const uint32_t n_tiles = (n + kDtokTile - 1) / kDtokTile;
-    HIP_TRY(c, c->d_state.reserve(sizeof(DtokState) + 64));
-    // (one kernel for the block, wk_dtok_fused.hpp: decided here, the words' mode checked again below)
-    bool fuse = emit && !extra && c->use_fused && c->dt_fmt == WK_FMT_SAM && c->w_open && c->w_mode == 0 && !c->dt_keep_reads &&
-                wkx_tok_n_names(tok) < (1 << 23) - 1;
-    // (text the one kernel keeps handing back -- runs longer than its window, say -- pays for both ways block after
-    // block: after two blocks in a row it is left out for 2, 4, ... 32 blocks before it is tried again)
-    if (fuse && c->fz_skip > 0) {
+    scan_lap(c, s, 0);
+    return WK_OK;
+}
+
+// The block's newlines per tile and their offsets into d_tiles / d_tile_off, the total into scalar 3, on the scan's
+// stream; `wait`: and the stream waited for, the count taken.
+static int scan_count_now(wk_ctx* c, ScanBlock& s, bool wait) {
+    const uint32_t n_tiles = (s.n + kDtokTile - 1) / kDtokTile;
+    HIP_TRY(c, c->d_tiles.reserve((size_t)n_tiles * 8));
+    HIP_TRY(c, c->d_tile_off.reserve((size_t)n_tiles * 8));
+    count_newlines(c->dt_text, s.n, c->d_tiles.as<unsigned long long>(), c->d_tile_off.as<unsigned long long>(), scalar_u64(c, 3), c->stream);
+    if (!wait) return WK_OK;
+    HIP_TRY(c, hipMemcpyAsync(&s.n_newlines, scalar_u64(c, 3), 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    s.tile_off = c->d_tile_off.as<unsigned long long>();
+    s.have_count = true;
+    return WK_OK;
+}
+
+// Which way does the block go, and how many lines has it?  The six kernels need the block's newlines per tile before
+// anything else; the one kernel counts its lines itself.  A block copied ahead while blocks went through the one
+// kernel (`fused_streak`) was not counted behind its copy: it is counted here only if it needs the six kernels -- it
+// may still turn out to (scan_line_starts) -- or if the sample's record buffers are still to be sized from its lines
+// per byte (wk_dtok_expect).
+static int scan_count(wk_ctx* c, ScanBlock& s) {
+    HIP_TRY(c, dtok_scratch_reserve(c));
+    s.fuse = s.emit && !s.extra && fused_eligible(c, s.tok);
+    if (s.fuse && c->fz_skip > 0) {   // (left out after blocks handed back in a row: fz_handed_back)
         --c->fz_skip;
-        fuse = false;
+        s.fuse = false;
     }
-    // The six kernels need the block's newlines per tile before anything else; the one kernel counts its lines itself.
-    // A block copied ahead while blocks went through the one kernel (`fused_streak`) was not counted behind its copy:
-    // it is counted here only if it turns out to need the six kernels after all -- or if the sample's record buffers
-    // are still to be sized from its lines per byte (wk_dtok_expect).
-    const bool ahead = !resident && counted_or_ahead;
-    KernelTimer* kt = ktimer_begin(c, "dtok_lines");
-    unsigned long long n_newlines = 0;
-    const unsigned long long* tile_off = nullptr;
-    bool have_count = false;
-    auto count_now = [&]() -> int {
-        HIP_TRY(c, c->d_tiles.reserve((size_t)n_tiles * 8));
-        HIP_TRY(c, c->d_tile_off.reserve((size_t)n_tiles * 8));
-        hipLaunchKernelGGL(dtok_count_kernel, dim3(n_tiles), dim3(kDtokThreads), 0, c->stream, c->dt_text, n,
-                           c->d_tiles.as<unsigned long long>());
-        hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_tiles.as<unsigned long long>(),
-                           c->d_tile_off.as<unsigned long long>(), (int64_t)n_tiles, scalar_u64(c, 3));
-        HIP_TRY(c, hipMemcpyAsync(&n_newlines, scalar_u64(c, 3), 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        tile_off = c->d_tile_off.as<unsigned long long>();
-        have_count = true;
-        return WK_OK;
-    };
-    const bool want_count = !fuse || (c->dt_expect_bytes > 0 && c->w_expect == 0);
-    if (res) {
+    s.kt = ktimer_begin(c, "dtok_lines");
+    if (s.where == ScanBlock::kResident) {
         // (the product counts a block's newlines behind its copy -- when the block is to take the six kernels -- and
         // never waits for them; here the same two kernels run in front of the scan, their result was taken at upload)
-        if (!fuse) {
-            HIP_TRY(c, c->d_tiles.reserve((size_t)n_tiles * 8));
-            HIP_TRY(c, c->d_tile_off.reserve((size_t)n_tiles * 8));
-            hipLaunchKernelGGL(dtok_count_kernel, dim3(n_tiles), dim3(kDtokThreads), 0, c->stream, c->dt_text, n,
-                               c->d_tiles.as<unsigned long long>());
-            hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_tiles.as<unsigned long long>(),
-                               c->d_tile_off.as<unsigned long long>(), (int64_t)n_tiles, scalar_u64(c, 3));
-        }
-        n_newlines = res->n_newlines;
-        tile_off = res->tile_off;
-        have_count = true;
-    } else if (counted) {  // (counted behind the copy: the number is on the host once the copy's event has passed)
+        int rc = 0;
+        if (!s.fuse && (rc = scan_count_now(c, s, false))) return rc;
+        s.n_newlines = s.res->n_newlines;
+        s.tile_off = s.res->tile_off;
+        s.have_count = true;
+    } else if (s.counted) {  // (counted behind the copy: the number is on the host once the copy's event has passed)
+        const TextBuf& b = c->text_buf[s.k];
         {
             Lap wait(&c->lap_s[3]);
-            HIP_TRY(c, hipEventSynchronize(c->copy_ev[k]));
+            HIP_TRY(c, hipEventSynchronize(b.ev));
         }
-        {
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, c->copy_ev0[k], c->copy_evm[k]) == hipSuccess) {
-                c->lap_copy_ms += ms;
-                c->lap_copy_bytes += n;
-            } else {
-                (void)hipGetLastError();
-            }
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, b.ev0, b.evm) == hipSuccess) {
+            c->lap_copy_ms += ms;
+            c->lap_copy_bytes += s.n;
+        } else {
+            (void)hipGetLastError();
         }
-        n_newlines = c->copy_newlines[k];
-        tile_off = c->d_tile_off_k[k].as<unsigned long long>();
-        have_count = true;
-    } else if (want_count) {
-        const int rc = count_now();
+        s.n_newlines = c->copy_newlines[s.k];
+        s.tile_off = b.tile_off.as<unsigned long long>();
+        s.have_count = true;
+    } else if (!s.fuse || (c->dt_expect_bytes > 0 && c->w_expect == 0)) {
+        const int rc = scan_count_now(c, s, true);
         if (rc) return rc;
     }
-    // a last line without newline (the byte was noted when the block was copied ahead: the host bytes of such a
-    // block may be gone)
-    const bool open_end = (ahead ? c->copy_last[k] : src[n - 1]) != '\n';
-    // (not counted: no more lines than bytes / 7 -- a mapped record is "q\tf\tr\t\n" at least -- and, once the
-    // sample has shown its lines per byte, a quarter more than that; the kernel reports records that find no room)
-    uint32_t lines = (uint32_t)n_newlines + (open_end ? 1u : 0u);
-    if (!have_count) {
-        double est = (double)n / 7.0 + 1.0;
-        if (c->dt_lpb > 0.0) est = std::min(est, (double)n * c->dt_lpb * 1.25 + 65536.0);
-        lines = (uint32_t)est;
+    // (the last byte was noted when the block was copied ahead: the host bytes of such a block may be gone)
+    s.open_end = (s.where == ScanBlock::kCopiedAhead ? c->text_buf[s.k].last : s.src[s.n - 1]) != '\n';
+    s.lines = s.have_count ? (uint32_t)s.n_newlines + (s.open_end ? 1u : 0u) : lines_at_most(c, s.n);
+    return WK_OK;
+}
+
+// The one kernel, waited for at once; *done: it kept the block and the caller has its answer.  Its scalars land in
+// slot 0 of the pinned scratch.  `fz_parity` moves on only when the block is kept.
+static int scan_try_fused(wk_ctx* c, ScanBlock& s, bool* done) {
+    c->dt_lines = s.lines;
+    int rc = dtok_mirror_dict(c, s.tok);
+    if (rc) return rc;
+    words_expect_from_block(c);   // (the block has been counted then: scan_count)
+    if ((rc = words_roll(c, s.lines))) return rc;
+    if ((rc = words_room(c, s.lines))) return rc;
+    // (words_roll may have reopened the job set: the block takes the six kernels then and counts as no hand-back)
+    const StreamSet streams = stream_set(c);
+    if (c->w_mode != 0 || streams.n_streams > kFzStreams) return WK_OK;
+    if (s.where == ScanBlock::kResident) ktimer_end(c, s.kt);   // (the count behind a resident block's "copy": its own family)
+    const int ring = c->fz_parity;
+    if ((rc = fused_launch(c, streams, c->dt_text, s.n, s.open_end, ring, 0, 0))) return rc;
+    c->w_backup_cur = fz_bk(c, ring).p;
+    scan_lap(c, s, 2);
+    DtokState st{};
+    {
+        Lap wait(&c->lap_s[2]);
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
-    if (c->d_unknown.cap < (size_t)(1 << 20) * 8) HIP_TRY(c, c->d_unknown.reserve((size_t)(1 << 20) * 8));
-    // The usual block of a sample whose words are open -- SAM text, records for the weighted histogram, every subject
-    // known -- goes through ONE kernel (wk_dtok_fused.hpp).  A block it hands back (a subject the dictionary does not
-    // hold, a line for the host tokenizer, a run or a line beyond its window) leaves the streams as they were and
-    // takes the six kernels below.
-    if (fuse) {
-        c->dt_lines = lines;
-        int rc = dtok_mirror_dict(c, tok);
-        if (rc) return rc;
-        if (c->dt_expect_bytes > 0 && c->w_expect == 0) {   // (have_count: see want_count)
-            const double expect = (double)c->dt_expect_bytes * ((double)lines / (double)n) * 1.08 + (double)lines;
-            c->w_expect = (int64_t)std::min(expect, (double)(1ll << 30));
-        }
-        if ((rc = words_roll(c, lines))) return rc;
-        if ((rc = words_room(c, lines))) return rc;
-        FusedArgs fa{};
-        fa.streams = stream_set(c);
-        if (c->w_mode == 0 && fa.streams.n_streams <= kFzStreams) {   // (words_roll may have reopened the job set)
-            fa.text = c->dt_text;
-            fa.n = n;
-            fa.open_end = open_end ? 1u : 0u;
-            const unsigned grid = fused_spans(c, n, &fa.span);
-            if (fa.span % 16u) return fail(c, WK_E_ARG, "spans of the one-kernel tokenizer are multiples of 16 bytes");
-            fa.dict8 = c->d_dict2.as<DictSlot8>();
-            fa.names16 = c->d_names16.as<uint4>();
-            fa.dict_mask = c->dt_dict_mask;
-            fa.arena = c->d_arena.as<unsigned char>();
-            fa.unknown = c->d_unknown.as<uint2>();
-            fa.unknown_cap = (uint32_t)(c->d_unknown.cap / 8);
-            fa.state = c->d_state.as<DtokState>();
-            fa.ablate = c->fused_ablate;
-            fa.submap = c->dt_submap_on ? c->d_submap.as<int32_t>() : nullptr;
-            fa.n_submap = c->dt_submap_n;
-            c->w_counts_known = false;
-            HIP_TRY(c, c->w_backup.reserve(kMaxStreams * 8));
-            HIP_TRY(c, c->w_backup2.reserve(kMaxStreams * 8));
-            // ONE launch per block while blocks follow one another through this kernel: its last workgroup leaves the
-            // cursors as they are behind the block in the other of two buffers -- the next block's "before" --, the
-            // block's scalars in pinned memory and cleared ones on the device.  (Anything else that moves the cursors
-            // or the scalars in between breaks the chain: the small kernel in front, then.)
-            HIP_TRY(c, c->w_backup3.reserve(kMaxStreams * 8));
-            DevBuf& before = fz_bk(c, c->fz_parity);
-            DevBuf& after = fz_bk(c, (c->fz_parity + 1) % 3);
-            fa.backup_prev = before.as<unsigned long long>();   // (the block's records: the cursors' advance over it)
-            fa.backup_next = after.as<unsigned long long>();
-            fa.host_state = reinterpret_cast<DtokState*>(c->host_back);   // (slot 0 of the pinned scratch)
-            c->w_backup_cur = before.p;
-            if (res) ktimer_end(c, kt);   // (the count behind a resident block's "copy": its own family)
-            KernelTimer* kf = ktimer_begin(c, "dtok_fused");
-            if (!c->fz_chain || c->fz_no_chain)
-                hipLaunchKernelGGL(dtok_fused_begin_kernel, dim3(1), dim3(64), 0, c->stream, before.as<unsigned long long>(),
-                                   (const unsigned long long*)fa.streams.cursor, fa.state);
-            hipLaunchKernelGGL(dtok_fused_kernel, dim3(grid), dim3(kFzThreads), 0, c->stream, fa);
-            ktimer_end(c, kf);
-            HIP_TRY(c, hipGetLastError());
-            lap_mark(2);
-            DtokState st{};
-            {
-                Lap wait(&c->lap_s[2]);
-                HIP_TRY(c, hipStreamSynchronize(c->stream));
-            }
-            small_back_get(c, 0, &st, sizeof st);
-            lap_t = std::chrono::steady_clock::now();
-            const bool keep = st.flags == 0 && st.n_unknown == 0;
-            int64_t nr = 0, nrec = 0;
-            c->dt_emitted = false;
-            if ((rc = dtok_emit_finish(c, keep, false, st, 0, &nr, &nrec))) return rc;   // (not kept: the cursors go back)
-            lap_mark(4);
-            c->fused_streak = keep;
-            c->fz_chain = keep;   // (not kept: dtok_emit_finish has put the cursors back)
-            if (keep) {
-                c->fz_parity = (c->fz_parity + 1) % 3;
-                c->fz_back_streak = 0;
-                ++c->fused_blocks;
-                lines = (uint32_t)st.n_lines + (open_end ? 1u : 0u);
-                c->dt_lines = lines;
-                c->dt_lpb = (double)lines / (double)n;
-                *status = 0;
-                *n_lines = lines;
-                *emit = 1;
-                emitted[0] = nr;
-                emitted[1] = nrec;
-                c->dt_ready = false;
-                return WK_OK;
-            }
-            ++c->fused_fallbacks;
-            fz_handed_back(c);
-            kt = ktimer_begin(c, "dtok_lines");
-        }
+    small_back_get(c, 0, &st, sizeof st);
+    s.lap_t = std::chrono::steady_clock::now();
+    const bool keep = st.flags == 0 && st.n_unknown == 0;
+    int64_t nr = 0, nrec = 0;
+    c->dt_emitted = false;
+    if ((rc = dtok_emit_finish(c, keep, false, st, 0, &nr, &nrec))) return rc;   // (not kept: the cursors go back)
+    scan_lap(c, s, 4);
+    if (!keep) {
+        fz_handed_back(c);
+        s.kt = ktimer_begin(c, "dtok_lines");
+        return WK_OK;
     }
-    if (!have_count) {  // (the six kernels after all)
-        const int rc = count_now();
+    c->fz_chain = true;
+    c->fz_parity = (ring + 1) % 3;
+    s.lines = fz_kept(c, st, s.n, s.open_end);
+    scan_reply_emitted(c, s, nr, nrec);
+    *done = true;
+    return WK_OK;
+}
+
+// Line starts (the first of the six kernels): offsets per tile -> positions.
+static int scan_line_starts(wk_ctx* c, ScanBlock& s) {
+    if (!s.have_count) {  // (the six kernels after all)
+        const int rc = scan_count_now(c, s, true);
         if (rc) return rc;
-        lines = (uint32_t)n_newlines + (open_end ? 1u : 0u);
+        s.lines = (uint32_t)s.n_newlines + (s.open_end ? 1u : 0u);
     }
     c->fused_streak = false;
     // (sized for a full block of short lines from the first block on: a file's first blocks are small, and
     // every growth is a hipFree -- which waits for the device -- and a hipMalloc per array)
-    const size_t cap_lines = std::max<size_t>(lines, (size_t)1 << 21);
+    const size_t cap_lines = std::max<size_t>(s.lines, (size_t)1 << 21);
     HIP_TRY(c, c->d_lines.reserve((cap_lines + 2) * 4));
     HIP_TRY(c, c->d_lsubj.reserve((cap_lines + 1) * 4));
     HIP_TRY(c, c->d_lmeta.reserve((cap_lines + 1) * 4));
     HIP_TRY(c, c->d_start.reserve(cap_lines + 64));
     HIP_TRY(c, c->d_first.reserve(cap_lines + 64));
-    if (extra) {
+    if (s.extra) {
         HIP_TRY(c, c->d_lbeg.reserve((cap_lines + 1) * 4));
         HIP_TRY(c, c->d_lend.reserve((cap_lines + 1) * 4));
         HIP_TRY(c, c->d_llen.reserve((cap_lines + 1) * 4));
         HIP_TRY(c, c->d_lscan.reserve((cap_lines + 1) * 8));
     }
     // (line 0 and the block's scalars are written by the lines kernel itself)
-    hipLaunchKernelGGL(dtok_lines_kernel, dim3(n_tiles), dim3(kDtokThreads), 0, c->stream, c->dt_text, n,
-                       tile_off, c->d_lines.as<uint32_t>(), c->d_state.as<DtokState>());
-    if (open_end) {
-        const uint32_t end = n + 1;  // as if a newline followed the text
-        HIP_TRY(c, hipMemcpyAsync(c->d_lines.as<uint32_t>() + lines, &end, 4, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(dtok_lines_kernel, dim3((s.n + kDtokTile - 1) / kDtokTile), dim3(kDtokThreads), 0, c->stream, c->dt_text, s.n,
+                       s.tile_off, c->d_lines.as<uint32_t>(), c->d_state.as<DtokState>());
+    if (s.open_end) {
+        const uint32_t end = s.n + 1;  // as if a newline followed the text
+        HIP_TRY(c, hipMemcpyAsync(c->d_lines.as<uint32_t>() + s.lines, &end, 4, hipMemcpyHostToDevice, c->stream));
     }
-    ktimer_end(c, kt);
+    ktimer_end(c, s.kt);
     HIP_TRY(c, hipGetLastError());
-    c->dt_lines = lines;
-    lap_mark(1);
-    // parse; subjects the dictionary does not know are interned in text order, then once more
+    c->dt_lines = s.lines;
+    scan_lap(c, s, 1);
+    return WK_OK;
+}
+
+// The subjects that the parse did not find in the dictionary (d_unknown: offset and length of each name) are
+// interned, in text order -- from the host's bytes, or from the device's where those are gone.
+static int scan_intern_unknown(wk_ctx* c, const ScanBlock& s, uint32_t n_unknown) {
+    std::vector<uint2> unk(n_unknown);
+    HIP_TRY(c, hipMemcpyAsync(unk.data(), c->d_unknown.p, (size_t)n_unknown * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    std::sort(unk.begin(), unk.end(), [](const uint2& x, const uint2& y) { return x.x < y.x; });
+    if (!c->dt_detached) {
+        for (const uint2& u : unk) (void)wkx_tok_intern(s.tok, s.src + u.x, u.y);
+        return WK_OK;
+    }
+    // the names come back from the device: one by one while they are few, with the whole block otherwise
+    const bool whole = unk.size() > 128;
+    size_t need = 0;
+    for (const uint2& u : unk) need += u.y;
+    std::vector<char> back(whole ? (size_t)s.n : need);
+    if (whole) {
+        HIP_TRY(c, hipMemcpyAsync(back.data(), c->dt_text, s.n, hipMemcpyDeviceToHost, c->stream));
+    } else {
+        size_t at = 0;
+        for (const uint2& u : unk) {
+            if (u.y) HIP_TRY(c, hipMemcpyAsync(back.data() + at, c->dt_text + u.x, u.y, hipMemcpyDeviceToHost, c->stream));
+            at += u.y;
+        }
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    size_t at = 0;
+    for (const uint2& u : unk) {
+        (void)wkx_tok_intern(s.tok, back.data() + (whole ? (size_t)u.x : at), u.y);
+        at += u.y;
+    }
+    return WK_OK;
+}
+
+// Parse (with the emission queued right behind it where the caller takes one); subjects the dictionary does not know
+// are interned, then once more.
+static int scan_parse_rounds(wk_ctx* c, ScanBlock& s) {
     for (int round = 0; round < 3; ++round) {
-        int rc = dtok_mirror_dict(c, tok);
+        int rc = dtok_mirror_dict(c, s.tok);
         if (rc) return rc;
         if (round > 0) HIP_TRY(c, hipMemsetAsync(c->d_state.p, 0, sizeof(DtokState), c->stream));  // (round 0: by dtok_lines_kernel)
         const DtokArgs a = dtok_args(c);
         c->dt_mapped = false;
-        kt = ktimer_begin(c, "dtok_parse");
-        if (extra)
-            hipLaunchKernelGGL(dtok_parse_kernel<true>, dim3((lines + kDtokThreads - 1) / kDtokThreads), dim3(kDtokThreads), 0, c->stream, a);
+        const dim3 grid((s.lines + kDtokThreads - 1) / kDtokThreads);
+        KernelTimer* kt = ktimer_begin(c, "dtok_parse");
+        if (s.extra)
+            hipLaunchKernelGGL(dtok_parse_kernel<true>, grid, dim3(kDtokThreads), 0, c->stream, a);
         else
-            hipLaunchKernelGGL(dtok_parse_kernel<false>, dim3((lines + kDtokThreads - 1) / kDtokThreads), dim3(kDtokThreads), 0, c->stream, a);
+            hipLaunchKernelGGL(dtok_parse_kernel<false>, grid, dim3(kDtokThreads), 0, c->stream, a);
         ktimer_end(c, kt);
         HIP_TRY(c, hipGetLastError());
-        lap_mark(2);
-        const bool speculate = emit && round == 0 && !extra && c->w_open && lines > 0;
+        scan_lap(c, s, 2);
+        const bool speculate = s.emit && round == 0 && !s.extra && c->w_open && s.lines > 0;
         bool ordered = false;
         unsigned long long totals = 0;
         if (speculate && (rc = dtok_emit_launch(c, &ordered, &totals))) return rc;
-        lap_mark(3);
+        scan_lap(c, s, 3);
         DtokState st{};
         static_assert(sizeof(DtokState) <= (size_t)wk_ctx::kBackBytes && sizeof(DtokState) % 4 == 0, "DtokState fits a slot");
         HIP_TRY(c, small_back(c, 0, c->d_state.p, sizeof st));
@@ -3890,61 +4009,60 @@ static int dtok_scan_impl(wk_ctx* c, wk_tok* tok, const char* text, int64_t begi
         }
         small_back_get(c, 0, &st, sizeof st);
         if (speculate && ordered) small_back_get(c, 1, &totals, 8);
-        lap_t = std::chrono::steady_clock::now();
+        s.lap_t = std::chrono::steady_clock::now();
         if (speculate) {
             const bool keep = st.flags == 0 && st.n_unknown == 0;
             int64_t nr = 0, nrec = 0;
             if ((rc = dtok_emit_finish(c, keep, ordered, st, totals, &nr, &nrec))) return rc;
-            lap_mark(4);
+            scan_lap(c, s, 4);
             if (keep) {
-                *status = 0;
-                *n_lines = lines;
-                *emit = 1;
-                emitted[0] = nr;
-                emitted[1] = nrec;
-                c->dt_ready = false;  // (nothing left for wk_dtok_emit)
+                scan_reply_emitted(c, s, nr, nrec);
                 return WK_OK;
             }
         }
         if (st.flags) return WK_OK;  // status 1: the host tokenizer takes the block
         if (st.n_unknown == 0) {
-            *status = 0;
-            *n_lines = lines;
+            *s.status = 0;
+            *s.n_lines = s.lines;
             c->dt_ready = true;
             return WK_OK;
         }
-        lap_t = std::chrono::steady_clock::now();
-        std::vector<uint2> unk(st.n_unknown);
-        HIP_TRY(c, hipMemcpyAsync(unk.data(), c->d_unknown.p, (size_t)st.n_unknown * 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        std::sort(unk.begin(), unk.end(), [](const uint2& x, const uint2& y) { return x.x < y.x; });
-        if (!c->dt_detached) {
-            for (const uint2& u : unk) (void)wkx_tok_intern(tok, src + u.x, u.y);
-        } else {
-            // the names come back from the device: one by one while they are few, with the whole block otherwise
-            const bool whole = unk.size() > 128;
-            size_t need = 0;
-            for (const uint2& u : unk) need += u.y;
-            std::vector<char> back(whole ? (size_t)n : need);
-            if (whole) {
-                HIP_TRY(c, hipMemcpyAsync(back.data(), c->dt_text, n, hipMemcpyDeviceToHost, c->stream));
-            } else {
-                size_t at = 0;
-                for (const uint2& u : unk) {
-                    if (u.y) HIP_TRY(c, hipMemcpyAsync(back.data() + at, c->dt_text + u.x, u.y, hipMemcpyDeviceToHost, c->stream));
-                    at += u.y;
-                }
-            }
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            size_t at = 0;
-            for (const uint2& u : unk) {
-                (void)wkx_tok_intern(tok, back.data() + (whole ? (size_t)u.x : at), u.y);
-                at += u.y;
-            }
-        }
-        lap_mark(5);
+        s.lap_t = std::chrono::steady_clock::now();
+        if ((rc = scan_intern_unknown(c, s, (uint32_t)st.n_unknown))) return rc;
+        scan_lap(c, s, 5);
     }
     return fail(c, WK_E_STATE, "device tokenizer: subjects still unknown after interning them");
+}
+
+// `emit` (may be null): with the words of this sample open (wk_words_begin), the emission is queued right behind the
+// parse — the usual block brings no subject the dictionary does not know — and the host waits once for both; *emit = 1
+// when the block's records have been appended that way (then emitted[0..1] = reads, records).
+static int dtok_scan_impl(wk_ctx* c, wk_tok* tok, const char* text, int64_t begin, int64_t stop, int extra, int64_t* n_lines, int* status,
+                          int* emit, int64_t* emitted) {
+    if (!c || !tok || !text || begin < 0 || stop < begin || !n_lines || !status) return WK_E_ARG;
+    if (emit) *emit = 0;
+    if (c->lag_count) return fail(c, WK_E_STATE, "blocks whose verdict has not been read (wk_dtok_scan_emit_end)");
+    Lap lap(&c->lap_s[1]);
+    ScanBlock s{tok, text + begin, 0, extra != 0, n_lines, status, emit, emitted};
+    if (!scan_checks(c, s, stop - begin)) return WK_OK;
+    DeviceGuard guard(c->device);
+    KtScope kt_scope(c);
+    c->dt_n = s.n;
+    c->dt_lines = 0;
+    if (s.n == 0) {
+        *status = 0;
+        c->dt_ready = true;
+        return WK_OK;
+    }
+    int rc;
+    if ((rc = scan_locate_text(c, s))) return rc;
+    if ((rc = scan_count(c, s))) return rc;
+    if (s.fuse) {
+        bool done = false;
+        if ((rc = scan_try_fused(c, s, &done)) || done) return rc;
+    }
+    if ((rc = scan_line_starts(c, s))) return rc;
+    return scan_parse_rounds(c, s);
 }
 
 // ---- the verdict of a block read one block late ------------------------------------------------------------------
@@ -3954,44 +4072,36 @@ static int dtok_scan_impl(wk_ctx* c, wk_tok* tok, const char* text, int64_t begi
 // it.  With two blocks under way the second one's kernel starts the moment the first one's ends.  A block the kernel
 // hands back (*status = 2) has left no record -- nor has the block launched behind it, which is forgotten: the caller
 // scans both again the synchronous way (their text is where it was).
+// (The launch is made as if the block will be kept: `fz_parity` moves on and `fz_chain` is set at once, `w_backup_cur`
+// is _end's to set when it keeps the block.  A hand-back does not rewind the parity: the broken chain seeds the next
+// launch's "before" again.)
 int wk_dtok_scan_emit_begin(wk_ctx* c, wk_tok* tok, const char* text, int64_t begin, int64_t stop, int* started) {
     if (!c || !tok || !text || begin < 0 || stop < begin || !started) return WK_E_ARG;
     *started = 0;
     const int64_t n64 = stop - begin;
-    if (!c->lag_enabled || !c->use_fused || c->lag_count >= 2 || c->fz_skip > 0 || c->dt_fmt != WK_FMT_SAM || !c->w_open || c->w_mode != 0 || c->dt_keep_reads ||
-        n64 <= 0 || n64 >= (1ll << 31) - 64 || wkx_tok_n_names(tok) >= (1 << 23) - 1)
-        return WK_OK;
+    if (!c->lag_enabled || c->lag_count >= 2 || c->fz_skip > 0 || n64 <= 0 || n64 >= (1ll << 31) - 64 || !fused_eligible(c, tok)) return WK_OK;
     if (!wkx_tok_device_ok(tok) && !c->dt_submap_on) return WK_OK;
     if (c->dt_expect_bytes > 0 && c->w_expect == 0) return WK_OK;   // (the sample's buffers are sized from a counted block)
     if (c->lag_count > 0 && !c->fz_chain) return WK_OK;
     DeviceGuard guard(c->device);
     const uint32_t n = (uint32_t)n64;
     const char* src = text + begin;
-    const wk_ctx::ResidentText* res = nullptr;
-    for (const wk_ctx::ResidentText& r : c->resident)
-        if (r.host == src && r.n == n) res = &r;
+    const wk_ctx::ResidentText* res = resident_text(c, src, n);
     int k = -1;
-    uint32_t lines = 0;
-    bool open_end;
     {
         std::lock_guard<std::mutex> lock(c->copy_mu);
-        if (c->lag_count == 0)
-            for (int q = 0; q < wk_ctx::kTextBufs; ++q)
-                if (c->buf_state[q] == wk_ctx::kBufScanning) c->buf_state[q] = wk_ctx::kBufFree;
-        if (!res) {
-            for (int q = 0; q < wk_ctx::kTextBufs; ++q)
-                if (c->buf_state[q] == wk_ctx::kBufCopied && c->copy_src[q] == src && c->copy_n[q] == n && (k < 0 || c->copy_seq[q] < c->copy_seq[k]))
-                    k = q;
-            if (k < 0) return WK_OK;   // (not copied ahead: the synchronous call copies it)
-        }
+        if (c->lag_count == 0) textbuf_release_scanned(c);
+        if (!res && (k = textbuf_find_copied(c, src, n)) < 0) return WK_OK;   // (not copied ahead: the synchronous call copies it)
     }
+    uint32_t lines = 0;
+    bool open_end;
     if (res) {
         open_end = src[n - 1] != '\n';
         lines = (uint32_t)res->n_newlines + (open_end ? 1u : 0u);
     } else {
         if (c->dt_lpb <= 0.0) return WK_OK;
-        open_end = c->copy_last[k] != '\n';
-        lines = (uint32_t)std::min((double)n / 7.0 + 1.0, (double)n * c->dt_lpb * 1.25 + 65536.0);
+        open_end = c->text_buf[k].last != '\n';
+        lines = lines_at_most(c, n);
     }
     // room for the records of every block under way (none of them is in w_records yet); a buffer that would have to
     // grow while a kernel appends to it, or a sample that would have to be rolled, waits for the verdicts
@@ -4011,36 +4121,17 @@ int wk_dtok_scan_emit_begin(wk_ctx* c, wk_tok* tok, const char* text, int64_t be
     }
     int rc = dtok_mirror_dict(c, tok);
     if (rc) return rc;
-    FusedArgs fa{};
-    fa.streams = stream_set(c);
-    if (fa.streams.n_streams > kFzStreams) return WK_OK;
+    const StreamSet streams = stream_set(c);
+    if (streams.n_streams > kFzStreams) return WK_OK;
     if (!res) {
-        std::lock_guard<std::mutex> lock(c->copy_mu);
-        c->buf_state[k] = wk_ctx::kBufPending;
-        c->copy_src[k] = nullptr;
-        c->copy_counted[k] = false;
+        {
+            std::lock_guard<std::mutex> lock(c->copy_mu);
+            textbuf_claim(c, k, wk_ctx::kBufPending);
+        }
+        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->text_buf[k].ev, 0));
     }
-    if (!res) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->copy_ev[k], 0));
-    HIP_TRY(c, c->d_state.reserve(sizeof(DtokState) + 64));
-    if (c->d_unknown.cap < (size_t)(1 << 20) * 8) HIP_TRY(c, c->d_unknown.reserve((size_t)(1 << 20) * 8));
-    for (int i = 0; i < 3; ++i) HIP_TRY(c, fz_bk(c, i).reserve(kMaxStreams * 8));
-    fa.text = res ? res->dev : c->d_textptr[k];
-    fa.n = n;
-    fa.open_end = open_end ? 1u : 0u;
-    const unsigned grid = fused_spans(c, n, &fa.span);
-    if (fa.span % 16u) return fail(c, WK_E_ARG, "spans of the one-kernel tokenizer are multiples of 16 bytes");
-    fa.dict8 = c->d_dict2.as<DictSlot8>();
-    fa.names16 = c->d_names16.as<uint4>();
-    fa.dict_mask = c->dt_dict_mask;
-    fa.arena = c->d_arena.as<unsigned char>();
-    fa.unknown = c->d_unknown.as<uint2>();
-    fa.unknown_cap = (uint32_t)(c->d_unknown.cap / 8);
-    fa.state = c->d_state.as<DtokState>();
-    fa.ablate = c->fused_ablate;
-    fa.submap = c->dt_submap_on ? c->d_submap.as<int32_t>() : nullptr;
-    fa.n_submap = c->dt_submap_n;
     wk_ctx::LagSlot& L = c->lag[c->lag_count];
-    L.buf = res ? -1 : k;
+    L.buf = k;
     L.src = src;
     L.n = n;
     L.open_end = open_end;
@@ -4050,25 +4141,10 @@ int wk_dtok_scan_emit_begin(wk_ctx* c, wk_tok* tok, const char* text, int64_t be
     if (!c->lag_ev[c->lag_next_ev]) HIP_TRY(c, hipEventCreateWithFlags(&c->lag_ev[c->lag_next_ev], hipEventDisableTiming));
     L.ev = c->lag_ev[c->lag_next_ev];
     c->lag_next_ev ^= 1;
-    fa.backup_prev = fz_bk(c, L.ring).as<unsigned long long>();   // (the block's records: the cursors' advance over it)
-    fa.backup_next = fz_bk(c, (L.ring + 1) % 3).as<unsigned long long>();
-    fa.host_state = reinterpret_cast<DtokState*>(c->host_back + (size_t)L.host_slot * wk_ctx::kBackBytes);
-    static_assert(sizeof(DtokState) <= 128 && wk_ctx::kBackBytes >= 132, "the slot's second half holds the block's sequence number");
-    L.seq = 0;
-    if (c->lag_poll) {
-        L.seq = ++c->lag_seq ? c->lag_seq : ++c->lag_seq;
-        fa.host_seq = reinterpret_cast<uint32_t*>(c->host_back + (size_t)L.host_slot * wk_ctx::kBackBytes + 128);
-        fa.seq = L.seq;
-    }
-    c->w_counts_known = false;
+    L.seq = 0;   // (the block's end is seen in pinned memory; without `lag_poll`, waited for through L.ev)
+    if (c->lag_poll) L.seq = ++c->lag_seq ? c->lag_seq : ++c->lag_seq;
     KtScope kt_scope(c);   // (wk_profile_kernels: a block queued behind another one is bracketed from that one's end to its own)
-    KernelTimer* kf = ktimer_begin(c, "dtok_fused");
-    if (!c->fz_chain || c->fz_no_chain)
-        hipLaunchKernelGGL(dtok_fused_begin_kernel, dim3(1), dim3(64), 0, c->stream, fz_bk(c, L.ring).as<unsigned long long>(),
-                           (const unsigned long long*)fa.streams.cursor, fa.state);
-    hipLaunchKernelGGL(dtok_fused_kernel, dim3(grid), dim3(kFzThreads), 0, c->stream, fa);
-    ktimer_end(c, kf);
-    HIP_TRY(c, hipGetLastError());
+    if ((rc = fused_launch(c, streams, res ? res->dev : c->text_buf[k].text, n, open_end, L.ring, L.host_slot, L.seq))) return rc;
     if (!c->lag_poll) HIP_TRY(c, hipEventRecord(L.ev, c->stream));
     // (the next block is launched as if this one will be kept: its kernel leaves what that needs behind)
     c->fz_chain = true;
@@ -4114,17 +4190,11 @@ int wk_dtok_scan_emit_end(wk_ctx* c, int64_t* n_lines, int* status, int64_t* n_r
         c->dt_emitted = false;
         const int rc = dtok_emit_finish(c, true, false, st, 0, n_reads, n_records);
         if (rc) return rc;
-        const uint32_t lines = (uint32_t)st.n_lines + (L.open_end ? 1u : 0u);
-        c->dt_lines = lines;
-        c->dt_lpb = (double)lines / (double)L.n;
-        c->fused_streak = true;
-        c->fz_back_streak = 0;
-        ++c->fused_blocks;
-        *n_lines = lines;
+        *n_lines = fz_kept(c, st, L.n, L.open_end);
         *status = 0;
         if (L.buf >= 0) {
             std::lock_guard<std::mutex> lock(c->copy_mu);
-            c->buf_state[L.buf] = wk_ctx::kBufFree;
+            c->text_buf[L.buf].state = wk_ctx::kBufFree;
         }
         c->lag[0] = c->lag[1];
         --c->lag_count;
@@ -4137,19 +4207,10 @@ int wk_dtok_scan_emit_end(wk_ctx* c, int64_t* n_lines, int* status, int64_t* n_r
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     {
         std::lock_guard<std::mutex> lock(c->copy_mu);
-        for (int i = 0; i < c->lag_count; ++i) {
-            const wk_ctx::LagSlot& X = c->lag[i];
-            if (X.buf < 0) continue;
-            c->buf_state[X.buf] = wk_ctx::kBufCopied;
-            c->copy_src[X.buf] = X.src;
-            c->copy_n[X.buf] = X.n;
-            c->copy_counted[X.buf] = false;
-        }
+        for (int i = 0; i < c->lag_count; ++i)
+            if (c->lag[i].buf >= 0) textbuf_retag(c, c->lag[i].buf, c->lag[i].src, c->lag[i].n);
     }
     c->lag_count = 0;
-    c->fz_chain = false;
-    c->fused_streak = false;
-    ++c->fused_fallbacks;
     fz_handed_back(c);
     *status = 2;
     return WK_OK;
@@ -4174,11 +4235,7 @@ int wk_dtok_scan_emit(wk_ctx* c, wk_tok* tok, const char* text, int64_t begin, i
 // totals), `finish` — once the stream has been waited for — accepts or discards what they wrote.
 static int dtok_emit_launch(wk_ctx* c, bool* ordered_out, unsigned long long* totals) {
     c->fz_chain = false;
-    if (c->dt_expect_bytes > 0 && c->w_expect == 0 && c->dt_n > 0) {
-        // (a record per line at most; 8 % on top of the first block's rate, never more than the 2^30 a pass holds)
-        const double lines = (double)c->dt_expect_bytes * ((double)c->dt_lines / (double)c->dt_n) * 1.08 + (double)c->dt_lines;
-        c->w_expect = (int64_t)std::min(lines, (double)(1ll << 30));
-    }
+    words_expect_from_block(c);
     int rc = words_roll(c, c->dt_lines);
     if (rc) return rc;
     if ((rc = words_room(c, c->dt_lines))) return rc;
@@ -4619,10 +4676,8 @@ int wk_strata_load(wk_ctx* c, const char* text, int64_t n64, int64_t* n_pairs, i
     HIP_TRY(c, c->s_tiles.reserve((size_t)n_tiles * 8));
     HIP_TRY(c, c->s_tile_off.reserve((size_t)n_tiles * 8));
     HIP_TRY(c, hipMemsetAsync(scalar_u64(c, 3), 0, 8, c->stream));
-    hipLaunchKernelGGL(dtok_count_kernel, dim3(n_tiles), dim3(kDtokThreads), 0, c->stream, c->s_text.as<unsigned char>(), n,
-                       c->s_tiles.as<unsigned long long>());
-    hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, c->stream, c->s_tiles.as<unsigned long long>(),
-                       c->s_tile_off.as<unsigned long long>(), (int64_t)n_tiles, scalar_u64(c, 3));
+    count_newlines(c->s_text.as<unsigned char>(), n, c->s_tiles.as<unsigned long long>(), c->s_tile_off.as<unsigned long long>(),
+                   scalar_u64(c, 3), c->stream);
     unsigned long long n_newlines = 0;
     HIP_TRY(c, hipMemcpyAsync(&n_newlines, scalar_u64(c, 3), 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
