@@ -102,7 +102,9 @@ __global__ void __launch_bounds__(kStrataThreads) strata_parse_kernel(StrataArgs
             tab = p;
             break;
         }
-        if (b == '\r') atomicOr(&s.state[0], kStrataOddBytes);  // (universal newlines: the line ends here)
+        // (universal newlines: the line ends here -- the \r of a \r\n ending, or of an open last line, ends a
+        // line that has no tab, which is no pair either way)
+        if (b == '\r' && p + 1u < hi) atomicOr(&s.state[0], kStrataOddBytes);
         kh.put(b);
     }
     bool pair = tab < hi;
