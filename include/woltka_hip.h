@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define WK_ABI_VERSION 4
+#define WK_ABI_VERSION 5
 
 /* error codes */
 #define WK_OK 0
@@ -281,6 +281,19 @@ int wk_host_register(wk_ctx* ctx, const void* p, size_t bytes);
 int wk_host_unregister(wk_ctx* ctx, const void* p);
 int wk_words_begin(wk_ctx* ctx, const wk_job* jobs, int32_t n_jobs,
                    int32_t group, int* ok);
+/* The reference classifies one chunk under every rank of the call
+ * (workflow.py:333-335 loops its ranks over the chunk), and its documented call
+ * mixes the kinds: `--rank none,free,phylum,...,species`.  wk_words_begin_mixed
+ * accepts what wk_words_begin accepts, with the same result, and in addition a
+ * set of at least one whole-read job (`--rank free`, a rank under --uniq /
+ * --above / --major above one half) next to at least one plain job (`--rank
+ * none`, a rank without those options), none of them WK_F_SIZED.  The sample's
+ * records are then kept once, in read order; wk_words_flush counts every
+ * whole-read job with the per-read stream and the plain jobs with the weighted
+ * histogram, each under its index in the set.  Every refusal of wk_words_begin
+ * for a job of either kind refuses the set (*ok = 0). */
+int wk_words_begin_mixed(wk_ctx* ctx, const wk_job* jobs, int32_t n_jobs,
+                         int32_t group, int* ok);
 int wk_words_append(wk_ctx* ctx, const uint32_t* words, int64_t n_records,
                     int64_t n_reads, int slot);
 int wk_words_wait(wk_ctx* ctx, int slot);

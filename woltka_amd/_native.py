@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get('WOLTKA_HIP_LIB') or os.path.join(
     _HERE, 'libwoltka_hip.so')
 
 # constants mirrored from include/woltka_hip.h
-ABI_VERSION = 4
+ABI_VERSION = 5
 OK, E_HIP, E_ARG, E_STATE, E_CAPACITY, E_RANGE, E_TABLE_FULL = (
     0, -1, -2, -3, -4, -5, -6)
 KEY_FEATURE_BITS, KEY_GROUP_BITS, KEY_K_BITS, KEY_JOB_BITS = 28, 21, 12, 3
@@ -43,7 +43,7 @@ SYMBOLS = (
     'wk_set_uniform_group', 'wk_chunk_download', 'wk_ordinal_hit_offsets',
     'wk_ordinal_pair_genes',
     'wk_blob_join', 'wk_table_body', 'wk_table_rows', 'wk_host_alloc', 'wk_host_free', 'wk_host_register', 'wk_host_unregister',
-    'wk_words_begin', 'wk_words_append',
+    'wk_words_begin', 'wk_words_begin_mixed', 'wk_words_append',
     'wk_words_wait', 'wk_words_flush', 'wk_words_pending',
     'wk_sized_pending', 'wk_sized_fetch',
     'wk_get_stats', 'wk_reset_stats', 'wk_timer_begin', 'wk_timer_end',
@@ -162,6 +162,8 @@ def load_library():
         'wk_host_unregister': (C.c_int, [p, C.c_void_p]),
         'wk_words_begin': (C.c_int, [p, C.POINTER(Job), C.c_int32, C.c_int32,
                                      C.POINTER(C.c_int)]),
+        'wk_words_begin_mixed': (C.c_int, [p, C.POINTER(Job), C.c_int32,
+                                           C.c_int32, C.POINTER(C.c_int)]),
         'wk_words_append': (C.c_int, [p, u32p, C.c_int64, C.c_int64, C.c_int]),
         'wk_words_wait': (C.c_int, [p, C.c_int]),
         'wk_words_flush': (C.c_int, [p]),
@@ -608,11 +610,14 @@ class Context:
         self._check(self._lib.wk_host_unregister(self._h,
                                                  C.c_void_p(int(address))))
 
-    def words_begin(self, jobs, group):
+    def words_begin(self, jobs, group, mixed=False):
+        """``mixed``: through ``wk_words_begin_mixed``, which also takes
+        whole-read jobs next to plain ones."""
         ok = C.c_int(0)
-        self._check(self._lib.wk_words_begin(self._h, self._jobs(jobs),
-                                             len(jobs), int(group),
-                                             C.byref(ok)))
+        begin = self._lib.wk_words_begin_mixed if mixed else \
+            self._lib.wk_words_begin
+        self._check(begin(self._h, self._jobs(jobs), len(jobs), int(group),
+                          C.byref(ok)))
         return bool(ok.value)
 
     def words_append(self, words, n_reads, slot=-1):

@@ -480,6 +480,7 @@ struct WeighMergeArgs {
     int32_t n_jobs;
     int32_t mode[WK_MAX_JOBS];
     int32_t col[WK_MAX_JOBS];
+    int32_t job_id[WK_MAX_JOBS];  // the job index of the count key per column of mode / col (a mixed set's plain jobs keep their places in the set)
     uint32_t group;
     CountTable table;
     uint32_t streams;                    // > 0: the slab of weigh_streams_kernel (rows of kSliceBins, per stream wg_first)
@@ -540,7 +541,7 @@ __global__ void __launch_bounds__(1024) weigh_merge_kernel(WeighMergeArgs a, uin
                     atomicOr(a.table.err, kErrFeatureRange);  // (cannot happen: such subjects are flagged)
                     continue;
                 }
-                cached_add(cache, a.table, make_key((uint32_t)jb, 0u, a.group, (uint32_t)f), w);
+                cached_add(cache, a.table, make_key((uint32_t)a.job_id[jb], 0u, a.group, (uint32_t)f), w);
             }
         }
     }

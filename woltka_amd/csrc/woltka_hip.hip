@@ -336,7 +336,8 @@ struct wk_ctx {
     };
     std::mutex reg_mu;
     std::vector<HostReg> regs;
-    int w_mode = 0;  // 0: subject indices for the weighted histogram; the stream of wk_free.hpp: 1: feature ids (one free-rank job), 2: ancestors at the job's rank (one rank job under --uniq / --above / --major), 3: subject indices, rewritten per job when the sample is classified (several such jobs)
+    int w_mode = 0;  // 0: subject indices for the weighted histogram; the stream of wk_free.hpp: 1: feature ids (one free-rank job), 2: ancestors at the job's rank (one rank job under --uniq / --above / --major), 3: subject indices, rewritten per job when the sample is classified (several such jobs), 4: subject indices read by both evaluators (whole-read jobs next to plain ones: wk_words_begin_mixed)
+    bool w_mixed_entry = false;  // the accumulation was opened by wk_words_begin_mixed (words_roll re-opens it there)
     int rank_serial = 0;              // bumped by wk_build_rank_table
     int free_per_cu = 2, free_threads = 1024, free_slots = 4096;  // launch shape of the free-rank stream (measurement knobs; DESIGN_HISTORY §3.1d)  // measurement knobs of the free-rank stream: workgroups per CU, windows in flight per wave
     int32_t max_gene_feature = 0;
@@ -2045,6 +2046,7 @@ int wk_classify_staged(wk_ctx* c, const wk_job* jobs, int32_t n_jobs, int32_t* o
                 for (int j = 0; j < n_jobs; ++j) {
                     wm.mode[j] = a.jobs[j].mode;
                     wm.col[j] = a.jobs[j].col;
+                    wm.job_id[j] = j;
                 }
                 wm.group = (uint32_t)a.group_base;
                 wm.table = a.table;
@@ -2254,40 +2256,84 @@ int wk_host_free(wk_ctx* c, void* p) {
 // Can the weighted histogram alone classify records under these jobs?  Plain
 // assigners only (see wk_weigh.hpp) and — checked against the current subject
 // table — every subject with an ancestor at every rank in use.
-static int words_jobs_ok(wk_ctx* c, const wk_job* jobs, int32_t n_jobs, ClassifyArgs& a, bool* ok, int* mode = nullptr) {
+// Does the job look at whole reads (the per-read stream of wk_free.hpp)?  `--rank free`, or a rank under --uniq, --above
+// or --major above one half; never a size-normalised job.
+static bool job_whole_reads(const wk_job& jb) {
+    if (jb.flags & WK_F_SIZED) return false;
+    if (jb.mode == WK_MODE_FREE) return true;
+    return jb.mode == WK_MODE_RANK && (jb.major > 0.5 || (jb.major <= 0.0 && (jb.flags & (WK_F_UNIQ | WK_F_ABOVE))));
+}
+
+// `mixed` (wk_words_begin_mixed): a set of whole-read jobs next to plain ones is taken too, as mode 4.  `a` then holds
+// the plain jobs alone, in the order of the set (a.n_jobs of them), and `plain_ids` (may be null) their indices in it.
+static int words_jobs_ok(wk_ctx* c, const wk_job* jobs, int32_t n_jobs, ClassifyArgs& a, bool* ok, int* mode = nullptr,
+                         bool mixed = false, int32_t* plain_ids = nullptr) {
     *ok = false;
     if (mode) *mode = 0;
     if (!c->use_weigh || c->n_subjects <= 0 || c->n_subjects > (int32_t)kWordSubjMask + 1) return WK_OK;
     // Jobs that look at whole reads — `--rank free` (classify.assign_free), a rank under --uniq, --above or --major above
     // one half (classify.assign_rank) — go to the per-read stream over node ids (wk_free.hpp): one such job with the
     // records rewritten as they are appended, several with the records rewritten per job when the sample is classified.
+    int n_stream = 0;
+    for (int j = 0; j < n_jobs; ++j) n_stream += job_whole_reads(jobs[j]) ? 1 : 0;
+    const bool mix = mixed && n_stream > 0 && n_stream < n_jobs;
+    bool stream_refuses = false;  // (a mixed set: its rows are built all the same, for the flush of what has been accumulated)
     {
-        int n_stream = 0;
-        for (int j = 0; j < n_jobs; ++j) {
-            const wk_job& jb = jobs[j];
-            if (jb.flags & WK_F_SIZED) continue;
-            if (jb.mode == WK_MODE_FREE)
-                n_stream += 1;
-            else if (jb.mode == WK_MODE_RANK && (jb.major > 0.5 || (jb.major <= 0.0 && (jb.flags & (WK_F_UNIQ | WK_F_ABOVE)))))
-                n_stream += 1;
-        }
-        if (n_stream == n_jobs && n_jobs >= 1) {
+        if ((n_stream == n_jobs && n_jobs >= 1) || mix) {
             if (c->n_nodes <= 0 || (uint32_t)c->n_nodes >= kFreeMissing) return WK_OK;
             for (int j = 0; j < n_jobs; ++j) {
                 const wk_job& jb = jobs[j];
+                if (!job_whole_reads(jb)) continue;  // (a mixed set's plain jobs: below)
                 if (jb.mode == WK_MODE_FREE) {
                     if (jb.flags & WK_F_SUBOK)  // a subject that is no node is its own result under --subok: not a feature the stream can carry
                         for (int32_t f : c->subj_feat_host)
-                            if (f >= c->n_nodes) return WK_OK;
+                            if (f >= c->n_nodes) {
+                                if (!mix) return WK_OK;
+                                stream_refuses = true;
+                                break;
+                            }
                 } else if (jb.rank_slot < 0 || jb.rank_slot >= (int)(sizeof c->rank_tab / sizeof c->rank_tab[0]) ||
                            !c->rank_tab_valid[jb.rank_slot]) {
                     return fail(c, WK_E_STATE, "job %d: rank slot %d has not been built", j, jb.rank_slot);
                 }
             }
-            if (mode) *mode = n_jobs > 1 ? 3 : jobs[0].mode == WK_MODE_FREE ? 1 : 2;
-            *ok = true;
-            return WK_OK;
+            if (!mix) {
+                if (mode) *mode = n_jobs > 1 ? 3 : jobs[0].mode == WK_MODE_FREE ? 1 : 2;
+                *ok = true;
+                return WK_OK;
+            }
         }
+    }
+    if (mix) {
+        // ---- the plain jobs of a mixed set: the checks and the subject rows of a plain set, over them alone
+        wk_job plain[WK_MAX_JOBS];
+        int32_t n_plain = 0;
+        a = ClassifyArgs{};
+        for (int j = 0; j < n_jobs; ++j) {
+            const wk_job& jb = jobs[j];
+            if (job_whole_reads(jb)) continue;
+            if (jb.flags & (WK_F_SIZED | WK_F_UNIQ)) return WK_OK;
+            if (jb.mode == WK_MODE_RANK) {
+                if ((jb.flags & WK_F_ABOVE) || jb.major > 0.0) return WK_OK;
+                if (jb.rank_slot < 0 || jb.rank_slot >= (int)(sizeof c->rank_tab / sizeof c->rank_tab[0]) || !c->rank_tab_valid[jb.rank_slot])
+                    return fail(c, WK_E_STATE, "job %d: rank slot %d has not been built", j, jb.rank_slot);
+            } else if (jb.mode != WK_MODE_NONE) {
+                return WK_OK;
+            }
+            JobDev d{};
+            d.mode = jb.mode;
+            d.flags = jb.flags;
+            d.major = jb.major;
+            a.jobs[n_plain] = d;
+            if (plain_ids) plain_ids[n_plain] = j;
+            plain[n_plain++] = jb;
+        }
+        a.n_jobs = n_plain;
+        const int rc = build_subject_rows(c, plain, n_plain, a);
+        if (rc) return rc;
+        *ok = !c->rows_any_invalid && !stream_refuses;
+        if (mode) *mode = 4;
+        return WK_OK;
     }
     a = ClassifyArgs{};
     a.n_jobs = n_jobs;
@@ -2558,15 +2604,19 @@ int wk_words_flush(wk_ctx* c) {
     if (c->w_mode != 0) {
         // ---- free-rank jobs and rank jobs that look at whole reads: per job, the stream over node ids, then its dense
         // counters into the count table.  One job: the records hold its node ids since they were appended; several:
-        // they hold subject indices, which the stream reads through the job's table (free_stream_kernel<., true>).
+        // they hold subject indices, which the stream reads through the job's table (free_stream_kernel<., true>).  A
+        // mixed set (mode 4): its whole-read jobs as the several of mode 3, each under its index in the set; the plain
+        // jobs are counted from the same records by the weighted histogram below.
         const int blocks = std::min(kStatBlocks, c->prop.multiProcessorCount * c->free_per_cu);
         const CountTable table{c->tkeys.as<unsigned long long>(), c->tvals.as<unsigned long long>(), c->slots - 1, scalar_err(c)};
-        if (c->w_mode != 3) {  // (subjects registered since the last chunk was appended)
+        if (c->w_mode != 3 && c->w_mode != 4) {  // (subjects registered since the last chunk was appended)
             const int rcr = refresh_word_ranks(c, c->w_records);
             if (rcr) return rcr;
         }
+        bool stats_counted = false;
         for (size_t j = 0; j < c->w_jobs.size(); ++j) {
             const wk_job& jb = c->w_jobs[j];
+            if (c->w_mode == 4 && !job_whole_reads(jb)) continue;
             const int kind = jb.mode == WK_MODE_FREE ? 1 : 2;
             wk_ctx::StreamTables& T = c->st[j];
             {
@@ -2575,7 +2625,7 @@ int wk_words_flush(wk_ctx* c) {
             }
             FreeArgs fa{};
             fa.words = c->c_words.as<uint32_t>();
-            const bool translate = c->w_mode == 3;  // (several jobs: the records hold subject indices, read through this job's table)
+            const bool translate = c->w_mode >= 3;  // (several jobs: the records hold subject indices, read through this job's table)
             fa.rank_of_subject = translate ? T.subj_rank.as<int32_t>() : nullptr;
             fa.n_subjects = (uint32_t)c->n_subjects;
             fa.err = scalar_err(c);
@@ -2591,7 +2641,8 @@ int wk_words_flush(wk_ctx* c) {
             fa.by_rank = kind == 2 ? 1u : 0u;
             fa.above = (jb.flags & WK_F_ABOVE) ? 1u : 0u;
             fa.major = kind == 2 ? jb.major : 0.0;
-            fa.count_stats = j == 0 ? 1u : 0u;  // (reads and records are counted once)
+            fa.count_stats = stats_counted ? 0u : 1u;  // (reads and records are counted once, by the first such job)
+            stats_counted = true;
             // the dense counters of the results (zero between launches: free_counts_kernel clears what it moves)
             const size_t dense_bytes = ((size_t)T.results + 1) * 4;
             if (c->f_dense.cap < dense_bytes || c->f_dense_tree != c->tree_serial) {  // (otherwise zero)
@@ -2645,23 +2696,32 @@ int wk_words_flush(wk_ctx* c) {
             ktimer_end(c, kt);
             HIP_TRY(c, hipGetLastError());
         }
-        if (c->words_keep) return WK_OK;
-        return words_reset(c);
+        if (c->w_mode != 4) {
+            if (c->words_keep) return WK_OK;
+            return words_reset(c);
+        }
     }
+    const bool mixed = c->w_mode == 4;
     ClassifyArgs a{};
     bool ok = false;
-    int rc = words_jobs_ok(c, c->w_jobs.data(), (int32_t)c->w_jobs.size(), a, &ok);
+    int32_t job_id[WK_MAX_JOBS];
+    for (int j = 0; j < WK_MAX_JOBS; ++j) job_id[j] = j;
+    int rc = words_jobs_ok(c, c->w_jobs.data(), (int32_t)c->w_jobs.size(), a, &ok, nullptr, mixed, job_id);
     if (rc) return rc;
+    if (mixed && !a.rows) return fail(c, WK_E_STATE, "the plain jobs of the mixed set have no subject rows");
     // (`ok` may be false by now: a subject without an ancestor at a rank in use
     // joined the table after these records.  wk_words_begin stops accepting
     // records the moment that happens, so every subject the accumulated records
     // name has a valid row — rows of old subjects do not change when the table
     // grows — and the new ones carry no weight.)
     (void)ok;
-    const int32_t n_jobs = (int32_t)c->w_jobs.size();
+    const int32_t n_jobs = mixed ? a.n_jobs : (int32_t)c->w_jobs.size();  // (a mixed set: its plain jobs, `job_id` their places in it)
     const uint32_t cus = (uint32_t)c->prop.multiProcessorCount;
+    // the one unsliced stream of the branches below: the first stream of the histogram's own accumulation, or a mixed
+    // set's records in read order
+    const uint32_t* const one_words = mixed ? c->c_words.as<uint32_t>() : c->w_stream[0].as<uint32_t>();
     // how many records every stream holds (known once per accumulation state)
-    if (!c->w_counts_known) {
+    if (!mixed && !c->w_counts_known) {
         HIP_TRY(c, hipMemcpyAsync(c->w_count, c->w_cursor.p, kMaxStreams * 8, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         c->w_counts_known = true;
@@ -2672,9 +2732,10 @@ int wk_words_flush(wk_ctx* c) {
         HIP_TRY(c, hipMemsetAsync(c->w_hi.p, 0, c->w_hi.cap, c->stream));
         c->w_hi_clean = c->w_hi.cap / 4;
     }
+    const unsigned long long one_count = mixed ? (unsigned long long)c->w_records : c->w_count[0];
     WeighMergeArgs wm{};
     KernelTimer* kt = nullptr;
-    if (c->w_sliced) {
+    if (c->w_sliced && !mixed) {
         // ---- a stream per slice of the subject table, each read once; workgroups in proportion to the streams' lengths
         StreamBinsArgs sa{};
         const int S = c->w_streams;
@@ -2735,8 +2796,8 @@ int wk_words_flush(wk_ctx* c) {
     } else if (c->weigh_wide || words_team_size(c) == 0) {
         // ---- more slices than a team has workgroups (wk_weigh_wide.hpp): the one stream partitioned by slice, then every
         // bucket read once
-        if (c->w_count[0] >= (1ull << 30)) return fail(c, WK_E_RANGE, "more than 2^30 records in one stream");
-        const uint32_t n = (uint32_t)c->w_count[0];
+        if (one_count >= (1ull << 30)) return fail(c, WK_E_RANGE, "more than 2^30 records in one stream");
+        const uint32_t n = (uint32_t)one_count;
         const uint32_t n_buckets = (uint32_t)streams_needed(c);  // (at most kWideMaxBuckets: words_jobs_ok)
         const uint32_t n_wg = std::min(c->weigh_wide_wgs > 0 ? (uint32_t)c->weigh_wide_wgs : cus, kWideMaxWgs);
         const uint32_t slab_rows = n_wg + n_buckets;
@@ -2752,9 +2813,9 @@ int wk_words_flush(wk_ctx* c) {
         const uint32_t n_tiles = (n + kWideTile - 1u) / kWideTile;
         const dim3 pgrid(std::max(1u, std::min(n_tiles, 2u * cus)));
         kt = ktimer_begin(c, "weigh_wide_part");
-        hipLaunchKernelGGL(wide_count_kernel, pgrid, dim3(kWideThreads), 0, c->stream, c->w_stream[0].as<uint32_t>(), n, n_buckets, bucket_count);
+        hipLaunchKernelGGL(wide_count_kernel, pgrid, dim3(kWideThreads), 0, c->stream, one_words, n, n_buckets, bucket_count);
         hipLaunchKernelGGL(wide_scan_kernel, dim3(1), dim3(256), 0, c->stream, bucket_count, n_buckets, n_wg, plan, cursor);
-        hipLaunchKernelGGL(wide_scatter_kernel, pgrid, dim3(kWideThreads), 0, c->stream, c->w_stream[0].as<uint32_t>(), n, n_buckets, cursor,
+        hipLaunchKernelGGL(wide_scatter_kernel, pgrid, dim3(kWideThreads), 0, c->stream, one_words, n, n_buckets, cursor,
                            c->w_wide.as<uint32_t>(), (uint32_t)std::min<size_t>(room, 0xFFFFFFFFu));
         ktimer_end(c, kt);
         WideBinsArgs wa{};
@@ -2784,9 +2845,9 @@ int wk_words_flush(wk_ctx* c) {
         const uint32_t n_teams = w_xcd * w_teams;
         HIP_TRY(c, c->w_slab.reserve((size_t)w_slices * n_teams * w_bins * 4));
         BinsArgs ba{};
-        ba.subj = c->w_stream[0].as<int32_t>();
+        ba.subj = reinterpret_cast<const int32_t*>(one_words);
         ba.rk = nullptr;
-        ba.n_records = (uint32_t)c->w_count[0];
+        ba.n_records = (uint32_t)one_count;
         ba.n_subjects = (uint32_t)c->n_subjects;
         ba.bins = w_bins;
         ba.n_slices = w_slices;
@@ -2822,19 +2883,22 @@ int wk_words_flush(wk_ctx* c) {
     for (int j = 0; j < n_jobs; ++j) {
         wm.mode[j] = a.jobs[j].mode;
         wm.col[j] = a.jobs[j].col;
+        wm.job_id[j] = job_id[j];
     }
     wm.group = (uint32_t)c->w_group;
     wm.table = CountTable{c->tkeys.as<unsigned long long>(), c->tvals.as<unsigned long long>(), c->slots - 1, scalar_err(c)};
     hipLaunchKernelGGL(weigh_merge_kernel, dim3((wm.n_subjects + kMergeSubjects - 1u) / kMergeSubjects), dim3(1024), (size_t)4096 * 16, c->stream, wm, 4096u);
     ktimer_end(c, kt);
     HIP_TRY(c, hipGetLastError());
-    c->stat_extra_reads += c->w_reads;
-    c->stat_extra_records += c->w_records;
+    if (!mixed) {  // (a mixed set: counted by its first whole-read job)
+        c->stat_extra_reads += c->w_reads;
+        c->stat_extra_records += c->w_records;
+    }
     if (c->words_keep) return WK_OK;  // (bench: repeated passes over the resident batch)
     return words_reset(c);
 }
 
-int wk_words_begin(wk_ctx* c, const wk_job* jobs, int32_t n_jobs, int32_t group, int* ok) {
+static int words_begin(wk_ctx* c, const wk_job* jobs, int32_t n_jobs, int32_t group, int* ok, bool mixed) {
     if (!c || !ok) return WK_E_ARG;
     *ok = 0;
     if (!jobs || n_jobs < 1 || n_jobs > WK_MAX_JOBS) return fail(c, WK_E_ARG, "n_jobs must be in [1,%d]", WK_MAX_JOBS);
@@ -2848,7 +2912,7 @@ int wk_words_begin(wk_ctx* c, const wk_job* jobs, int32_t n_jobs, int32_t group,
     ClassifyArgs a{};
     bool good = false;
     int mode = 0;
-    int rc = words_jobs_ok(c, jobs, n_jobs, a, &good, &mode);
+    int rc = words_jobs_ok(c, jobs, n_jobs, a, &good, &mode, mixed);
     if (rc) return rc;
     if (!good) {
         // (what is there was appended while every subject was valid: classify it now)
@@ -2864,9 +2928,18 @@ int wk_words_begin(wk_ctx* c, const wk_job* jobs, int32_t n_jobs, int32_t group,
     c->w_jobs.assign(jobs, jobs + n_jobs);
     c->w_group = group;
     c->w_mode = mode;
+    c->w_mixed_entry = mixed;
     c->w_open = true;
     *ok = 1;
     return WK_OK;
+}
+
+int wk_words_begin(wk_ctx* c, const wk_job* jobs, int32_t n_jobs, int32_t group, int* ok) {
+    return words_begin(c, jobs, n_jobs, group, ok, false);
+}
+
+int wk_words_begin_mixed(wk_ctx* c, const wk_job* jobs, int32_t n_jobs, int32_t group, int* ok) {
+    return words_begin(c, jobs, n_jobs, group, ok, true);
 }
 
 static StreamSet stream_set(wk_ctx* c) {
@@ -2961,10 +3034,11 @@ static int words_roll(wk_ctx* c, int64_t n_more) {
     if (c->w_records + n_more < (1ll << 30) && !outgrown) return WK_OK;
     const std::vector<wk_job> jobs = c->w_jobs;
     const int32_t group = c->w_group;
+    const bool mixed = c->w_mixed_entry;  // (re-opened through the gate that opened it)
     int rc = wk_words_flush(c);
     if (rc) return rc;
     int ok = 0;
-    if ((rc = wk_words_begin(c, jobs.data(), (int32_t)jobs.size(), group, &ok))) return rc;
+    if ((rc = words_begin(c, jobs.data(), (int32_t)jobs.size(), group, &ok, mixed))) return rc;
     if (!ok) return fail(c, WK_E_STATE, "job set no longer accepted");
     if (n_more >= (1ll << 30)) return fail(c, WK_E_RANGE, "more than 2^30 records in one block");
     return WK_OK;

@@ -1578,6 +1578,7 @@ class DeviceTextRoute:
             # (scanned and appended in one call, `wk_dtok_scan_emit`)
             dmaps = self._dmaps
             ROUTES['dtok_maps' if dmaps is not None else 'dtok'] += 1
+            self._count_mixed()
             self._n_reads += done
             if dmaps is not None and done:
                 self._device_maps(sample, *dmaps)
@@ -1595,7 +1596,7 @@ class DeviceTextRoute:
         t1 = time.perf_counter()
         if self.sizes:      # (rows of the samples flushed so far, once many)
             self._collect_sized(force=False)
-        began = self.ctx.words_begin(self.jobs, group)
+        began = self._words_begin(group)
         t2 = time.perf_counter()
         lap['subjects'] = lap.get('subjects', 0.0) + t1 - t0
         lap['begin'] = lap.get('begin', 0.0) + t2 - t1
@@ -1609,6 +1610,7 @@ class DeviceTextRoute:
             if status == 0:
                 ROUTES['dcover' if cover else
                        'dtok_maps' if dmaps is not None else 'dtok'] += 1
+                self._count_mixed()
                 self._n_reads += n_reads
                 if dmaps is not None and n_reads:
                     self._device_maps(sample, *dmaps)

@@ -1,18 +1,61 @@
 """Packed records accumulated per sample (wk_words_*): the weighted histogram
 for plain ranks (csrc/wk_weigh.hpp) and the per-read stream for `--rank free`
-/ `--uniq` / `--above` / `--major` (csrc/wk_free.hpp); which job sets they take."""
+/ `--uniq` / `--above` / `--major` (csrc/wk_free.hpp), both over one
+accumulation for a set that mixes the two kinds; which job sets they take."""
 import os
 
 import numpy as np
 
 from .. import _native as nat
-from ..hostio import MAX_GROUPS
+from ..hostio import MAX_GROUPS, ROUTES
+
+
+def whole_reads(job):
+    """Does the job look at whole reads?  `--rank free`, a rank under --uniq /
+    --above / --major above one half: the per-read stream (csrc/wk_free.hpp).
+    Never a size-normalised job."""
+    if job.flags & nat.F_SIZED:
+        return False
+    if job.mode == nat.MODE_FREE:
+        return True
+    return job.mode == nat.MODE_RANK and (
+        job.major > 0.5 or (job.major <= 0 and bool(
+            job.flags & (nat.F_UNIQ | nat.F_ABOVE))))
+
+
+def plain_job_ok(job):
+    """Is the job one the weighted histogram takes (csrc/wk_weigh.hpp)?"""
+    if job.flags & nat.F_UNIQ:
+        return False
+    if job.mode == nat.MODE_RANK and (job.flags & nat.F_ABOVE or
+                                      job.major > 0):
+        return False
+    return job.mode in (nat.MODE_NONE, nat.MODE_RANK)
 
 
 class WordsRoute:
     """(mixin of classify.Engine)"""
 
-    def words_eligible(self, identity=True, sized=False):
+    def words_mixed(self):
+        """Does the job set hold whole-read jobs next to other jobs?  Such a
+        set goes through ``wk_words_begin_mixed`` (`_words_begin`)."""
+        n = sum(map(whole_reads, self.jobs))
+        return 0 < n < len(self.jobs)
+
+    def _words_begin(self, group):
+        """The job set declared for the records that follow: through the
+        mixed entry when the set is mixed (``WOLTKA_NO_MIXED=1``: never)."""
+        return self.ctx.words_begin(self.jobs, group, mixed=self._mixed_on())
+
+    def _mixed_on(self):
+        return self.words_mixed() and not os.environ.get('WOLTKA_NO_MIXED')
+
+    def _count_mixed(self):
+        """A block or chunk appended under a mixed set (`ROUTES['mixed']`)."""
+        if self._mixed_on():
+            ROUTES['mixed'] += 1
+
+    def words_eligible(self, identity=True, sized=False, mixed=False):
         """Can chunks go to the device as packed words, accumulated per
         sample (``wk_words_*``)?  The plain assigners only — what
         ``wk_words_begin`` checks once more against the subject table.
@@ -22,7 +65,10 @@ class WordsRoute:
         plain classification of a whole file); then a set of plain
         size-normalised jobs is eligible too — its flush makes the rows of
         the contribution log (csrc/wk_sized.hpp, `_collect_sized`).  Sized
-        jobs that look at whole reads keep the general route."""
+        jobs that look at whole reads keep the general route.
+        ``mixed``: the caller declares the set through ``_words_begin``; then
+        whole-read jobs next to plain ones, none of them sized, are eligible
+        too (``WOLTKA_NO_MIXED=1``: not)."""
         if (self.sizes and not sized) or self._replay is not None or \
                 len(self.jobs) > nat.MAX_JOBS or \
                 (identity and not self._tok_identity) or \
@@ -31,25 +77,14 @@ class WordsRoute:
         # jobs that look at whole reads — `--rank free`, a rank under --uniq /
         # --above / --major above one half — all go to the per-read stream
         # (csrc/wk_free.hpp), alone or several of them
-        def whole_reads(job):
-            if job.flags & nat.F_SIZED:
-                return False
-            if job.mode == nat.MODE_FREE:
-                return True
-            return job.mode == nat.MODE_RANK and (
-                job.major > 0.5 or (job.major <= 0 and bool(
-                    job.flags & (nat.F_UNIQ | nat.F_ABOVE))))
         if all(map(whole_reads, self.jobs)):
             return self.use_tree
-        for job in self.jobs:
-            if job.flags & nat.F_UNIQ:
-                return False
-            if job.mode == nat.MODE_RANK and (job.flags & nat.F_ABOVE or
-                                              job.major > 0):
-                return False
-            if job.mode not in (nat.MODE_NONE, nat.MODE_RANK):
-                return False
-        return True
+        if mixed and self._mixed_on():
+            # (the plain jobs of the set: what the histogram takes, unsized)
+            return bool(self.use_tree) and all(
+                plain_job_ok(job) and not job.flags & nat.F_SIZED
+                for job in self.jobs if not whole_reads(job))
+        return all(map(plain_job_ok, self.jobs))
 
     @staticmethod
     def sized_on_device(plain, part=None):
@@ -108,8 +143,9 @@ class WordsRoute:
                 self._reserve(8 * len(self.subjects) * len(self.jobs))
         if self.sizes:      # (rows of the samples flushed so far, once many)
             self._collect_sized(force=False)
-        if self.ctx.words_begin(self.jobs, group):
+        if self._words_begin(group):
             self.ctx.words_append(words, n, slot)
+            self._count_mixed()
             # the buffer of the chunk before this one has been copied by now
             if self._ring_prev is not None:
                 self.ctx.words_wait(self._ring_prev)

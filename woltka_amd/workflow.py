@@ -468,15 +468,19 @@ def classify(
                         # (`--sizes`: the flush of a sample's words makes the
                         # rows of the contribution log, csrc/wk_sized.hpp)
                         sized = engine.sized_on_device(plain, part)
+                        # (whole-read jobs next to plain ones, the documented
+                        # `--rank none,free,phylum,...`: one accumulation read
+                        # by both evaluators, wk_words_begin_mixed)
                         words = plain and not trimsub and \
-                            engine.words_eligible(sized=sized)
+                            engine.words_eligible(sized=sized, mixed=True)
                         # (`--trim-sub`: the device text route translates the
                         # names it meets into subjects; the host tokenizer's
                         # words cannot)
                         # (`--exclude`: the names of the set get no subject
                         # index, so the tokenizer's ids are none either)
                         words_dev = plain and bool(trimsub or exclude) and \
-                            engine.words_eligible(identity=False, sized=sized)
+                            engine.words_eligible(identity=False, sized=sized,
+                                                  mixed=True)
                         # read maps of plain assigners, one sample per file:
                         # the lines are formatted on the device next to the
                         # tokenised text (csrc/wk_readmap.hpp)
