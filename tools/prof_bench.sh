@@ -19,13 +19,19 @@ f=$(find "$OUT/kt" -name "*kernel_stats.csv" 2>/dev/null | head -1)
 [ -n "$f" ] && cp "$f" "$OUT/kernel_stats.csv" && cut -c1-150 "$OUT/kernel_stats.csv" | head -8
 i=0
 # (PMC_SETS=traffic: the two passes the traffic figure needs, nothing else; insts: the instruction counts alone;
-# traffic+insts: both)
+# traffic+insts: both; cycles: how busy the waves and the vector units are, alone; insts+cycles, traffic+insts+cycles;
+# none: the kernel trace alone)
 sets=("FETCH_SIZE" "WRITE_SIZE")
 INSTS="SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_INSTS_VALU SQ_INSTS_SALU"
+CYCLES="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY"
+[ "${PMC_SETS:-all}" = none ] && sets=()
 [ "${PMC_SETS:-all}" = insts ] && sets=("$INSTS")
+[ "${PMC_SETS:-all}" = cycles ] && sets=("$CYCLES")
+[ "${PMC_SETS:-all}" = insts+cycles ] && sets=("$INSTS" "$CYCLES")
 [ "${PMC_SETS:-all}" = traffic+insts ] && sets+=("$INSTS")
+[ "${PMC_SETS:-all}" = traffic+insts+cycles ] && sets+=("$INSTS" "$CYCLES")
 [ "${PMC_SETS:-all}" = all ] && sets+=("SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE" "TCC_HIT_sum TCC_MISS_sum" "$INSTS")
-for set in "${sets[@]}"; do
+for set in ${sets[@]+"${sets[@]}"}; do
   i=$((i+1))
   timeout -k 10 900 rocprofv3 --pmc $set --output-format csv -d "$OUT/pmc$i" -- $CMD > "$OUT/pmc$i.log" 2>&1
   rc=$?; echo "pmc$i rc=$rc"

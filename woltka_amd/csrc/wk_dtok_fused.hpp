@@ -294,13 +294,13 @@ constexpr uint32_t kFiSubj = (1u << 23) - 1u;   // subject index (all ones: not 
 constexpr uint32_t kFiMateShift = 24;
 constexpr uint32_t kFiMapped = 1u << 26;
 constexpr uint32_t kFiStart = 1u << 27;          // starts a run of equal QNAMEs
-constexpr uint32_t kFiUndecided = 1u << 28;      // (between the line pass and the pass behind it) the lane below could not say whether the line starts a run
+constexpr uint32_t kFiUndecided = 1u << 28;      // (between the line pass and the search behind it) the lane below could not say whether the line starts a run
 constexpr uint32_t kFiExcl = 1u << 29;           // names a subject of the exclusion set
 constexpr uint32_t kFiDropped = 1u << 30;        // (on the line that starts a run) a line of the run does: the run is dropped whole
 constexpr uint32_t kFiRead = kFiMapped | (3u << kFiMateShift);          // same read of a run: same mate (and mapped)
 constexpr uint32_t kFiKey = kFiRead | kFiSubj;                          // ... and the same subject
 constexpr uint32_t kFzPad = 8;                   // words in front of the lines' words (the duplicate walk reads eight at a time; nothing walks ahead any more)
-constexpr uint32_t kFzEdgeMeta = 4;            // a line's summary at a seam of the line pass: words 0-3 the bytes, this one FnLine::meta
+static_assert(kFwWave == kWave && kFwWaves == kFzWaves, "the line pass's dealing is this workgroup's");
 
 // The 0x80 marks of two words (bits 7, 15, 23, 31 of each) as bits 0-7, the first word's in the low nibble: the second
 // word's marks go between the first one's (bits 4, 12, 20, 28), and one multiplication gathers all eight.  (Mark 8j [+4]
@@ -334,9 +334,6 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
     __shared__ __attribute__((aligned(16))) unsigned char txt[kFzChunks * 16 + 32];
     __shared__ uint16_t ls[kFzLines + 2];                                    // line starts (window offsets); ls[k + 1] - 1 = the newline of line k
     __shared__ uint16_t f_qn[kFzLines];                                      // QNAME length (the lines the lane below does not settle, and a run put aside)
-    // The line pass's 64-line groups at their seams (wk_dtok_neighbour.hpp): [g][0] the summary of group g's first line,
-    // [g][1] that of the line in front of it -- group g - 1's last; nothing in front of group 0.  Five words of eight.
-    __shared__ __attribute__((aligned(16))) uint32_t edge[kFzLines / kWave + 1][2][8];
     __shared__ __attribute__((aligned(16))) uint32_t info_[kFzPad + kFzCarry + kFzLines + kFzPad + 8];
     __shared__ uint32_t carry[kFzCarry];                                     // the words of a run's lines seen in windows before this one
     __shared__ unsigned long long planes[kFpPlanes][kFpWords];               // the owned lines as bits: run starts, first lines per mate (wk_dtok_planes.hpp)
@@ -347,7 +344,8 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
     __shared__ uint32_t wtot[kFzWaves];
     __shared__ unsigned long long gbase_out[kMaxStreams];                    // (the last workgroup) the streams' advance over the block
     __shared__ unsigned long long wg_totals;                                 // reads | lines << 32 of this workgroup (the exit)
-    __shared__ uint32_t own[4];                                              // first run start in the span, first at or behind its end, last of the window; the lines put aside
+    __shared__ uint32_t own[5];                                              // first run start in the span, first at or behind its end, last of the window; the lines put aside;
+                                                                             // [4]: a wave holds a line its lane below did not settle (the search pass is needed)
     __shared__ uint32_t wg_flags;
     uint32_t* const info = info_ + kFzPad + kFzCarry;  // (lines of the window from 0 up, the carried lines of its first run below 0)
 
@@ -363,7 +361,6 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
     if (tid < 4u) reinterpret_cast<uint32_t*>(txt + kFrTailChunk * 16u)[tid] = 0u;  // (no wave's chunk and never text: wk_dtok_rounds.hpp)
     if (tid == 0) wg_flags = 0u;
     if (tid == 0) wg_totals = 0ull;
-    if (tid == 0) edge[0][1][kFzEdgeMeta] = 0u;  // (its `meta`: no line in front of group 0; never written again)
     uint32_t my_flags = 0, my_reads = 0, my_lines = 0;
     const uint32_t text_end = a.n + (a.open_end ? 1u : 0u);  // (a text without a last newline: as if one followed)
 
@@ -421,7 +418,7 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
         const bool to_end = w1 == text_end;   // every line from here to the end of the text is whole
         const bool last_win = wide || w1 == span_w1;  // the span's last window: kFzFwd bytes behind the span, or the end of the text
         __syncthreads();  // (the window before is through with the arrays)
-        if (tid < 3u) own[tid] = tid < 2u ? 0xFFFFFFFFu : 0u;
+        if (tid < 5u) own[tid] = tid < 2u ? 0xFFFFFFFFu : 0u;
         // (a walk back stops in front of the carried lines at the latest; it never gets there: their first one starts the run)
         if (tid < kFzPad) info[-(int32_t)nc - 1 - (int32_t)tid] = kFiStart;
         for (uint32_t i = tid; i < nc; i += kFzThreads) info[(int32_t)i - (int32_t)nc] = carry[i];
@@ -522,16 +519,19 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
         if (tid == 0 && first_line) info[0] = 0u;
 
         // ---- a thread per line: three tabs, FLAG, RNAME; its subject; does it start a run? ----
-        // Line k is lane (k - first_line) % 64's, so the line before it is the lane below's: a mapped line at or behind
-        // t0 learns from that lane's summary whether it starts a run (wk_dtok_neighbour.hpp) while the dictionary slot
-        // of its subject is on its way.  What the neighbour does not settle -- it is unmapped, the QNAMEs are longer
-        // than 16 bytes and agree that far, the window's first line; and every wave's first lane, whose neighbour is
-        // another wave's -- is marked kFiUndecided and settled behind the barrier.  (Every lane takes every trip: the
-        // lanes exchange words.  The lines behind the last owned run are looked up for nothing: the rest of one run,
-        // and once per span what the kFzFwd bytes behind it hold.)
-        for (uint32_t k0 = first_line; k0 < n_lines; k0 += kFzThreads) {
-            const uint32_t k = k0 + tid;
-            const bool has = k < n_lines;
+        // Lanes 1..63 of a wave own 63 consecutive lines and lane 0 is their witness (wk_dtok_neighbour.hpp): it sums up
+        // the line in front of them once more and owns nothing, so the line before a lane's line is the lane below's in
+        // every wave.  A mapped line at or behind t0 learns from that lane's summary whether it starts a run while the
+        // dictionary slot of its subject is on its way.  What the neighbour does not settle -- it is unmapped, the QNAMEs
+        // are longer than 16 bytes and agree that far, the window's first line where nothing says it starts a run -- is
+        // marked kFiUndecided, the wave says so in own[4], and the search behind the barrier settles it.  (Every lane
+        // takes every trip: the lanes exchange words.  The lines behind the last owned run are looked up for nothing:
+        // the rest of one run, and once per span what the kFzFwd bytes behind it hold.)
+        // (the line the window before stopped at, or the first of the text: it starts a run, no search needed)
+        const bool first_starts = nc == 0u && (mode == 1u || wpos == 0u);
+        for (uint32_t k0 = first_line; k0 < n_lines; k0 += kFwTrip) {
+            const uint32_t k = fw_line(k0, wave, lane);
+            const bool has = fw_has(k, first_line, n_lines), owner = !fw_witness(lane);
             uint32_t word = 0, s = 0, qn = 0, rb = 0, rn = 0;
             unsigned long long q0 = 0ull, q1 = 0ull;
             if (has) {
@@ -590,29 +590,26 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
                         if (mate == 3u) my_flags |= kDtokBothMates;
                         word = kFiMapped | (mate << kFiMateShift);
                         qn = tab[0] - s;
-                        f_qn[k] = (uint16_t)qn;
+                        if (owner) f_qn[k] = (uint16_t)qn;
                     }
                 }
             }
             // (every lane again)  The subject of a mapped line at or behind t0 (only a first window has lines in front
             // of it): the first slot is asked for here and looked at behind the exchange.
-            const bool mapped = (word & kFiMapped) != 0u, look = mapped && w0 + s >= t0;
+            const bool mapped = (word & kFiMapped) != 0u, look = owner && mapped && w0 + s >= t0;
             const unsigned char* const name = txt + rb;
             FzProbe probe;
             if (look && !(ablate & 1u)) probe = fz_probe_begin(a, name, rn);
-            // the line's summary one lane up; lane 0 takes "no line" and asks the group's seam behind the barrier
+            // the line's summary one lane up; the witness takes "no line" and has no use for it
             const FnLine me = has ? fn_line(mapped, qn, q0, q1) : fn_no_line();
             FnLine prev;
             prev.meta = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)me.meta, 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
 #pragma unroll
             for (uint32_t i = 0; i < 4; ++i) prev.b[i] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)me.b[i], 0x138, 0xF, 0xF, false);
-            const uint32_t verdict = (ablate & 8u) ? (uint32_t)kFnStarts : (uint32_t)fn_verdict(prev, me);
-            if (lane == 0 || lane == kWave - 1u) {
-                uint32_t* const to = lane == 0 ? edge[(k0 - first_line) / kWave + wave][0] : edge[(k0 - first_line) / kWave + wave + 1u][1];
-                *reinterpret_cast<uint4*>(to) = make_uint4(me.b[0], me.b[1], me.b[2], me.b[3]);
-                to[kFzEdgeMeta] = me.meta;
-            }
+            const uint32_t verdict = ((ablate & 8u) || (first_starts && k == first_line)) ? (uint32_t)kFnStarts : (uint32_t)fn_verdict(prev, me);
             const bool start = look && verdict == kFnStarts;
+            const unsigned long long b_und = __ballot(look && verdict == kFnUndecided);  // (every lane votes: not behind `lane == 0 &&`)
+            if (lane == 0 && b_und != 0ull) own[4] = 1u;  // (every such wave stores the same word)
             if (look) {
                 int32_t sid = (ablate & 1u) ? (int32_t)(fz_load32(name + 4) % 1000u) : fz_probe_end(a, probe, name, rn, w0 + rb);
                 bool excluded = false;
@@ -631,9 +628,9 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
                 word |= (start ? kFiStart : 0u) | (verdict == kFnUndecided ? kFiUndecided : 0u) | (excluded ? kFiExcl : 0u) |
                         (sid < 0 ? kFiSubj : ((uint32_t)sid & kFiSubj));
             }
-            if (has) info[k] = word;  // (the line's whole word, once)
-            // The window's run starts: k rises with the lane, so a wave's first and last are its ballots' lowest and
-            // highest bits -- one lane tells own[].
+            if (has && owner) info[k] = word;  // (the line's whole word, once)
+            // The window's run starts: k rises with the lane (the witness's is one below lane 1's and raises no bit), so
+            // a wave's first and last are its ballots' lowest and highest bits -- one lane tells own[].
             const unsigned long long b_all = __ballot(start), b_in = __ballot(start && w0 + s < t1), b_out = b_all & ~b_in;
             if (lane == 0 && b_all) {
                 if (b_in) atomicMin(&own[0], k + (uint32_t)__builtin_ctzll(b_in));
@@ -642,33 +639,19 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
             }
         }
         __syncthreads();
-        // ---- what the lane below did not settle: the seams between the groups, then the search back ----
-        // (a wave's first lane: the same verdict from its group's seam, one read and no loop.  The rest is what every
-        // mapped line used to do: the mapped line before it searched for, the QNAMEs compared byte by byte -- behind a
-        // wave-uniform branch that text of short QNAMEs and few unmapped lines enters for a span's first window only.)
+        // ---- what the lane below did not settle: the search back ----
+        // (What every mapped line used to do: the mapped line before it searched for, the QNAMEs compared byte by byte.
+        // own[4], read behind the barrier and the same in every thread, says whether any wave holds such a line: text
+        // of short QNAMEs and few unmapped lines hardly ever comes here (a first window's lines in front of t0 are
+        // neighbours like any other), and a window that does not skips this pass and the barrier that closes it.  The
+        // starts of the line pass are in own[0..2] behind the barrier above.  Lines are dealt k0 + tid here: a line's
+        // word is read from info[], whoever wrote it.)
+        if (__builtin_amdgcn_readfirstlane((int)own[4])) {
         for (uint32_t k0 = first_line; k0 < n_lines; k0 += kFzThreads) {
             const uint32_t k = k0 + tid;
             const uint32_t mk = k < n_lines ? info[k] : 0u;
-            bool und = (mk & kFiUndecided) != 0u, start = false;
-            if (lane == 0 && und) {
-                const uint32_t g = (k0 - first_line) / kWave + wave;  // (g = 0: the window's first line)
-                FnLine before, me;
-#pragma unroll
-                for (uint32_t i = 0; i < 4; ++i) {
-                    before.b[i] = edge[g][1][i];
-                    me.b[i] = edge[g][0][i];
-                }
-                before.meta = edge[g][1][kFzEdgeMeta];
-                me.meta = edge[g][0][kFzEdgeMeta];
-                const FnVerdict v = fn_verdict(before, me);
-                und = v == kFnUndecided;
-                start = v == kFnStarts;
-                // (the line the window before stopped at, or the first of the text: it starts a run, no search needed)
-                if (g == 0u && nc == 0u && (mode == 1u || wpos == 0u)) {
-                    und = false;
-                    start = true;
-                }
-            }
+            const bool und = (mk & kFiUndecided) != 0u;
+            bool start = false;
             if (__ballot(und) != 0ull) {  // (wave-uniform)
                 if (und) {
                     uint32_t j = k;
@@ -700,6 +683,7 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
             }
         }
         __syncthreads();
+        }
         // Owned lines [ka, kb): from the first run that starts in the span (a first window), the window's first line or
         // the carried lines (below 0) to the first run that starts at or behind the span's end, or -- where the window
         // sees none -- to the last run start it sees: that run may go on behind the window, and the next window begins

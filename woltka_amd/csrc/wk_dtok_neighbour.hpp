@@ -1,13 +1,19 @@
 // wk_dtok_neighbour.hpp — does a line start a run?  Asked of the line before it alone (wk_dtok_fused.hpp).
 //
-// The line pass of the one-kernel tokenizer deals line k to lane k - first_line (mod 64) of a wave, so the line before
-// a lane's line is the lane below's.  Each lane sums its line up in five words -- is there a line, is it mapped, the
-// QNAME's length, and the QNAME's first 16 bytes (those behind its end cleared) -- and hands them one lane up; the 64th
-// lane's go through LDS to the next wave's first.  fn_verdict says what the two summaries settle: a QNAME of at most 16
-// bytes is compared whole, a longer one can be told apart from the one before by its length or its first 16 bytes and
-// is left to the kernel's byte compare where those agree.  A line whose neighbour is no mapped line (the window's
-// first line, a line behind unmapped ones) is left to the kernel's search as well.  Plain functions, the same on the
-// host and on the device: tests/test_dtok_neighbour_host.py holds them against a byte compare of whole QNAMEs.
+// The line pass of the one-kernel tokenizer deals the lines of a window so that the line before a lane's line is always
+// the lane below's, inside one wave: lanes 1..63 of a wave own 63 consecutive lines, and lane 0 is a *witness* -- it
+// sums up the line in front of the wave's first own line once more (the last own line of the wave before, or of thread
+// 511's wave in the trip before) and owns nothing: no probe, no word of `info[]` or `f_qn[]`, no bit in the ballots of
+// run starts.  A trip of the workgroup's eight waves covers 8 x 63 = 504 lines (fw_line, fw_has below).  Only the
+// window's first line has no line for its witness.  Each lane sums its line up in five words -- is there a line, is it
+// mapped, the QNAME's length, and the QNAME's first 16 bytes (those behind its end cleared) -- and hands them one lane
+// up; nothing goes through LDS and no lane waits for another wave.  fn_verdict says what the two summaries settle: a
+// QNAME of at most 16 bytes is compared whole, a longer one can be told apart from the one before by its length or its
+// first 16 bytes and is left to the kernel's byte compare where those agree.  A line whose neighbour is no mapped line
+// (the window's first line, a line behind unmapped ones) is left to the kernel's search as well; a wave that holds such
+// a line says so in one word of LDS, and a window in which no wave does skips the search pass and its barrier.  Plain
+// functions, the same on the host and on the device: tests/test_dtok_neighbour_host.py holds the verdict against a byte
+// compare of whole QNAMEs, tests/test_dtok_witness_host.py the dealing against plain enumeration.
 #pragma once
 #include <cstdint>
 
@@ -55,5 +61,20 @@ WK_FN_FN FnVerdict fn_verdict(const FnLine& prev, const FnLine& cur) {
     if (diff) return kFnStarts;
     return (cur.meta & kFnQn) <= kFnBytes ? kFnContinues : kFnUndecided;
 }
+
+// ---- the dealing: 63 owners and a witness per wave ----
+constexpr uint32_t kFwWave = 64;                      // lanes of a wave
+constexpr uint32_t kFwWaves = 8;                      // waves of a workgroup
+constexpr uint32_t kFwOwners = kFwWave - 1u;          // lines a wave owns per trip
+constexpr uint32_t kFwTrip = kFwWaves * kFwOwners;    // lines a trip of the workgroup covers (504)
+
+// The line of lane `lane` of wave `wave` in the trip that begins at line k0 (= first_line + 504 * trip): lanes 1..63
+// own k0 + 63 * wave + lane - 1, lane 0 looks at the line in front of them.  (Unsigned: wave 0's witness of a window
+// whose lines count from 0 gets 2^32 - 1, which fw_has turns down.)
+WK_FN_FN uint32_t fw_line(uint32_t k0, uint32_t wave, uint32_t lane) { return k0 + kFwOwners * wave + lane - 1u; }
+WK_FN_FN bool fw_witness(uint32_t lane) { return lane == 0u; }
+// is k one of the window's whole lines [first_line, n_lines)?  (first_line is 0 or 1)
+WK_FN_FN bool fw_has(uint32_t k, uint32_t first_line, uint32_t n_lines) { return k + 1u > first_line && k < n_lines; }
+// (the line pass takes its trips as  for (k0 = first_line; k0 < n_lines; k0 += kFwTrip))
 
 }  // namespace wk
