@@ -102,7 +102,9 @@ struct FusedArgs {
     StreamSet streams;
     const int32_t* submap;      // tokenizer id -> subject index, when they differ (`--trim-sub`), or null
     uint32_t n_submap;
-    uint32_t ablate;            // (measurement, wk_tune "fz_ablate": phases left out -- results are wrong then)
+    uint32_t ablate;            // (measurement, wk_tune "fz_ablate": phases left out -- results are wrong then.  Read by
+                                // dtok_fused_measure_kernel alone, which is launched when the word is not 0; bits 1 to 512 are
+                                // tested, so 1024 runs that instance with nothing left out: tests/test_gpu_dtok_instances.py)
 };
 
 // The block's reads (low half) and lines (high half) while the kernel runs: one word behind the DtokState, so that a
@@ -330,7 +332,11 @@ __device__ __forceinline__ uint32_t fz_tabs32(const unsigned char* p, unsigned l
     return m;
 }
 
-__global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu(6, 6))) dtok_fused_kernel(FusedArgs a) {
+// The kernel's body.  kMeasure = false is the product's kernel: FusedArgs::ablate is not read and every test of it
+// folds away; kMeasure = true is the measuring instance of tools/fused_ablate.py, with the phases `ablate` names left
+// out at run time (results are wrong then).  Both are instances of this one text: what is measured is what runs.
+template <bool kMeasure>
+__device__ __forceinline__ void dtok_fused_body(const FusedArgs& a) {
     __shared__ __attribute__((aligned(16))) unsigned char txt[kFzChunks * 16 + 32];
     __shared__ uint16_t ls[kFzLines + 2];                                    // line starts (window offsets); ls[k + 1] - 1 = the newline of line k
     __shared__ uint16_t f_qn[kFzLines];                                      // QNAME length (the lines the lane below does not settle, and a run put aside)
@@ -352,7 +358,7 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
     const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
     const uint32_t wave_s = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave);  // (in a scalar register: what depends on it alone is wave-uniform)
     const uint32_t n_streams = a.streams.n_streams;
-    const uint32_t ablate = a.ablate;
+    const uint32_t ablate = kMeasure ? a.ablate : 0u;
     const int32_t* const submap = a.submap;
     // (the buffers' fill: the word in LDS is added to by the records loop alone; `fill` is what every thread read there
     // behind that loop's barrier, the same in all of them)
@@ -370,14 +376,18 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
     // not full leaves with the one that is.)  `have`: the buffers' fill, packed as fill_packed is.
     auto flush_all = [&](unsigned long long have, bool last) {
         __syncthreads();
-        if (tid < n_streams) {
-            const uint32_t cnt = (ablate & 64u) ? 0u : (uint32_t)(have >> (16u * tid)) & 0xFFFFu;
-            unsigned long long base = 0ull;
-            if (cnt) {
-                base = atomicAdd(&a.streams.cursor[tid], (unsigned long long)cnt);
-                if (base + cnt > a.streams.cap) atomicOr(&wg_flags, kDtokSpill);
+        if (wave_s == 0u) {  // (the first wave's lanes, one per slice: a scalar test, and the compare made here)
+            uint32_t xl = lane;
+            asm volatile("" : "+v"(xl));
+            if (xl < n_streams) {
+                const uint32_t cnt = (ablate & 64u) ? 0u : (uint32_t)(have >> (16u * xl)) & 0xFFFFu;
+                unsigned long long base = 0ull;
+                if (cnt) {
+                    base = atomicAdd(&a.streams.cursor[xl], (unsigned long long)cnt);
+                    if (base + cnt > a.streams.cap) atomicOr(&wg_flags, kDtokSpill);
+                }
+                gbase[xl] = base;
             }
-            gbase[tid] = base;
         }
         __syncthreads();
         for (uint32_t k = 0; k < n_streams; ++k) {
@@ -394,7 +404,7 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
     // thread: the arguments, and words of LDS read behind a barrier.)
     const uint32_t t0 = blockIdx.x * a.span;   // (< n: the grid is ceil(n / span))
     const uint32_t t1 = a.n - t0 > a.span ? t0 + a.span : a.n;
-    const uint32_t span_w1 = (uint32_t)min((unsigned long long)t1 + kFzFwd, (unsigned long long)text_end);
+    const uint32_t span_w1 = fr_min_end(t1, kFzFwd, text_end);  // (min(t1 + kFzFwd, text_end) without the 64-bit sum: wk_dtok_rounds.hpp)
     uint32_t wpos = t0 >= kFzBack ? t0 - kFzBack : 0u;  // the window's first byte of text
     uint32_t mode = 0u;       // 0: the span's first window; 1: the line at wpos starts a run; 2: it is not known whether it does
     uint32_t counted = t0;    // the newlines in front of this position are in my_lines (windows of a span overlap)
@@ -413,20 +423,33 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
         const uint32_t w0 = wpos & ~15u;
         const uint32_t lead = wpos - w0;  // bytes of the line before in the first chunk (the first window begins at a chunk)
         // text positions [w0, w1) are looked at
-        const uint32_t w1 = (uint32_t)min((mode == 0u ? (unsigned long long)t0 + kFzTile + kFzFwd : (unsigned long long)w0 + kFzWin),
-                                           (unsigned long long)(wide ? text_end : span_w1));
+        const uint32_t w1 = fr_min_end(mode == 0u ? t0 : w0, mode == 0u ? kFzTile + kFzFwd : kFzWin, wide ? text_end : span_w1);
         const bool to_end = w1 == text_end;   // every line from here to the end of the text is whole
         const bool last_win = wide || w1 == span_w1;  // the span's last window: kFzFwd bytes behind the span, or the end of the text
         __syncthreads();  // (the window before is through with the arrays)
-        if (tid < 5u) own[tid] = tid < 2u ? 0xFFFFFFFFu : 0u;
-        // (a walk back stops in front of the carried lines at the latest; it never gets there: their first one starts the run)
-        if (tid < kFzPad) info[-(int32_t)nc - 1 - (int32_t)tid] = kFiStart;
+        // The wave's index once more, as a scalar of this window's own (see the exit for the thread's): what is decided
+        // by it below -- the first wave's stores, the rounds a wave runs, the waves in front of it -- is a scalar
+        // compare made where it is used.  Compares with `wave_s` itself are the same in every window, and the compiler
+        // makes each of them once, as a 64-bit mask of lanes in a pair of scalar registers the kernel does not have: a
+        // lane of a VGPR written in front of the loop and two lane reads per use.
+        uint32_t ws = wave_s;
+        asm volatile("" : "+s"(ws));
+        // (the first wave's lanes, found by a scalar test and compares with constants made here: the lane's number as
+        // a value of its own, so that no mask and no word is kept through the window for these stores -- see the exit)
+        if (ws == 0u) {
+            uint32_t xl = lane;
+            asm volatile("" : "+v"(xl));
+            if (xl < 5u) own[xl] = xl < 2u ? 0xFFFFFFFFu : 0u;
+            // (a walk back stops in front of the carried lines at the latest; it never gets there: their first one starts the run)
+            if (xl < kFzPad) info[-(int32_t)nc - 1 - (int32_t)xl] = kFiStart;
+        }
         for (uint32_t i = tid; i < nc; i += kFzThreads) info[(int32_t)i - (int32_t)nc] = carry[i];
 
         // ---- the window into LDS; newlines per 16-byte chunk ----
         // (a wave takes consecutive chunks, in full rounds -- wk_dtok_rounds.hpp: no barrier inside the scan below, and
         // the waves of two rounds skip the third, uniformly)
-        const uint32_t wave_c0 = fr_first_chunk(wave_s), wave_rounds = fr_rounds(wave_s);
+        // (wave_c0 goes into the lanes' addresses, which are kept; ws_c0 is the same number for the scalar tests)
+        const uint32_t wave_c0 = fr_first_chunk(wave_s), ws_c0 = fr_first_chunk(ws), wave_rounds = fr_rounds(ws);
         uint4 v[kFzRounds];
 #pragma unroll
         for (uint32_t r = 0; r < kFzRounds; ++r) {  // (all loads under way before the first is looked at.  Loading a window ahead, the
@@ -450,8 +473,8 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
             // newlines are this span's to count -- none of the corrections of the other branch applies.  (Almost
             // every round of almost every window; what touches the window's or the span's ends or the overlap with
             // the window before goes the other way.)
-            const uint32_t rp0 = w0 + (wave_c0 + r * kWave) * 16u;  // (the wave's first chunk of the round)
-            const bool interior = rp0 >= in_lo && (unsigned long long)rp0 + kWave * 16u <= in_hi;
+            const uint32_t rp0 = w0 + (ws_c0 + r * kWave) * 16u;  // (the wave's first chunk of the round)
+            const bool interior = rp0 >= in_lo && fr_fits(rp0, kWave * 16u, in_hi);
             *reinterpret_cast<uint4*>(txt + c * 16u) = v[r];
             if (interior) {  // (wave-uniform, scalar compares)
                 const uint32_t m = fr_chunk_marks(fz_newlines16(v[r]), &blank);
@@ -463,7 +486,7 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
                 uint32_t m = fz_newlines16(v[r]);
                 if (p + 16u > a.n) m &= p >= a.n ? 0u : (1u << (a.n - p)) - 1u;  // (nothing behind n is text)
                 if (p >= counted && p < t1) my_lines += (uint32_t)__popc(m);     // (the block's lines: counted in the span they end in, once)
-                if (a.open_end && a.n >= p && a.n < p + 16u) m |= 1u << (a.n - p);  // (n itself ends an open last line)
+                if (a.n - p < 16u) m |= a.open_end << (a.n - p);  // (n in [p, p + 16) ends an open last line: open_end is 0 or 1)
                 if (p + 16u > w1) m &= (1u << (w1 - p)) - 1u;
                 if (p < wpos) m &= ~((1u << (wpos - p)) - 1u);                   // (the tail of the line before is no text of this window)
                 m = fr_chunk_marks(m, &blank);
@@ -477,11 +500,14 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
         const uint32_t nl_wave = fz_last_lane(nl_inc);
         if (lane == 0) wtot[wave] = fr_total(nl_wave);
         __syncthreads();
+        // (the waves' counts as scalars -- every lane reads the same words --, so that "the waves in front" is a scalar
+        // compare with the wave's index and no mask of threads is kept through the window for it)
         uint32_t before = 0, total_nl = 0;
 #pragma unroll
         for (uint32_t w = 0; w < kFzWaves; ++w) {
-            before += w < wave ? wtot[w] : 0u;
-            total_nl += wtot[w];
+            const uint32_t t = (uint32_t)__builtin_amdgcn_readfirstlane((int)wtot[w]);
+            before += w < ws ? t : 0u;
+            total_nl += t;
         }
         // lines of the window: line k = [ls[k], ls[k + 1] - 1), k < total_nl whole (line 0 of a span's first window only
         // when it starts the text: that window begins in the middle of a line, the others at one)
@@ -926,6 +952,15 @@ __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu
             if (a.host_seq) __hip_atomic_store(a.host_seq, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
+}
+
+// the product's kernel
+__global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu(6, 6))) dtok_fused_kernel(FusedArgs a) {
+    dtok_fused_body<false>(a);
+}
+// the same with the measurement switches of wk_tune "fz_ablate" (launched exactly when that word is not 0)
+__global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu(6, 6))) dtok_fused_measure_kernel(FusedArgs a) {
+    dtok_fused_body<true>(a);
 }
 
 }  // namespace wk

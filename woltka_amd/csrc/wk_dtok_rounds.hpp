@@ -48,6 +48,15 @@ WK_FR_FN uint32_t fr_first_chunk(uint32_t w) {
     return w < kFrLongWaves ? w * 3u * kFrWave : kFrLongWaves * 3u * kFrWave + (w - kFrLongWaves) * 2u * kFrWave;
 }
 
+// Window limits in 32 bits.  min(base + len, lim) as 64-bit arithmetic gives it, for every 32-bit base, len and lim,
+// without the 64-bit sum: where lim <= base the sum is the larger one (lim); where lim > base, lim - base does not wrap
+// and "lim - base > len" says the same as "base + len < lim" -- and then the sum is below lim and does not wrap.
+// Nothing is asked of the block's size.  (tests/test_dtok_limits32_host.py holds both against the 64-bit forms at the
+// edges of the 32-bit range.)
+WK_FR_FN uint32_t fr_min_end(uint32_t base, uint32_t len, uint32_t lim) { return lim > base && lim - base > len ? base + len : lim; }
+// is base + len <= lim?  (lim - len does not wrap where lim >= len)
+WK_FR_FN bool fr_fits(uint32_t base, uint32_t len, uint32_t lim) { return lim >= len && base <= lim - len; }
+
 // the newlines of a chunk as they are counted: the mask, or none and `*blank` set where there are more than kFrChunkMax
 WK_FR_FN uint32_t fr_chunk_marks(uint32_t marks16, bool* blank) {
     if ((uint32_t)__builtin_popcount(marks16) > kFrChunkMax) {

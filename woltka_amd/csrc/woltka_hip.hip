@@ -3743,7 +3743,11 @@ static int fused_launch(wk_ctx* c, const StreamSet& streams, const unsigned char
     if (!c->fz_chain)
         hipLaunchKernelGGL(dtok_fused_begin_kernel, dim3(1), dim3(64), 0, c->stream, fz_bk(c, ring).as<unsigned long long>(),
                            (const unsigned long long*)streams.cursor, fa.state);
-    hipLaunchKernelGGL(dtok_fused_kernel, dim3(grid), dim3(kFzThreads), 0, c->stream, fa);
+    // (the measuring instance exactly when a phase is to be left out: the product's kernel holds no switch)
+    if (c->fused_ablate != 0u)
+        hipLaunchKernelGGL(dtok_fused_measure_kernel, dim3(grid), dim3(kFzThreads), 0, c->stream, fa);
+    else
+        hipLaunchKernelGGL(dtok_fused_kernel, dim3(grid), dim3(kFzThreads), 0, c->stream, fa);
     ktimer_end(c, kf);
     HIP_TRY(c, hipGetLastError());
     return WK_OK;
