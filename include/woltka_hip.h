@@ -584,6 +584,28 @@ int wk_dtok_stage_reads(wk_ctx* ctx, int64_t* n_reads, int64_t* n_records,
 int wk_demux_fetch(wk_ctx* ctx, int32_t* group, int64_t group_cap,
                    unsigned char* met, int32_t met_cap);
 
+/* Plain classification with `--stratify` on the device
+ * (csrc/wk_strata_reads.hpp; classify.counter_strat, classify.py:216-249): a
+ * query is counted under the stratum its read id -- QNAME, with "/1" | "/2"
+ * for a mate -- has in the sample's map, and skipped when the map does not
+ * hold it.
+ *   wk_dtok_stage_reads_strata  behind a wk_dtok_scan of the plain flavour
+ *                      (status 0), with a map loaded and its labels' groups
+ *                      given (wk_strata_load, wk_strata_groups) and
+ *                      demultiplexing off: run starts, the subject map and the
+ *                      exclusion set (wk_dtok_subject_map), then the block as
+ *                      the staged classify chunk, as wk_dtok_stage_reads
+ *                      leaves it -- a read's group is its label's, -1 for a
+ *                      read the map does not hold (not counted).
+ *                      wk_classify_staged follows.  *status != 0: nothing is
+ *                      staged, the host tokenizer takes the block (a read of
+ *                      more than WK_MAX_K subjects, a name without a subject).
+ *   wk_chunk_groups    group[0, n_reads) of the chunk either of the two
+ *                      entries staged last (cap >= n_reads). */
+int wk_dtok_stage_reads_strata(wk_ctx* ctx, int64_t* n_reads,
+                               int64_t* n_records, int* status);
+int wk_chunk_groups(wk_ctx* ctx, int32_t* group, int64_t cap);
+
 /* Convenience: stage + classify in one call from host buffers. */
 int wk_classify_chunk(wk_ctx* ctx, const wk_job* jobs, int32_t n_jobs,
                       const int32_t* subj, const int32_t* qoff,

@@ -65,6 +65,7 @@ SYMBOLS = (
     'wk_strata_groups', 'wk_strata_clear',
     'wk_demux_begin', 'wk_demux_pending', 'wk_demux_register',
     'wk_dtok_stage_reads', 'wk_demux_fetch',
+    'wk_dtok_stage_reads_strata', 'wk_chunk_groups',
     'wk_tok_subjects',
     'wk_tok_new_subjects', 'wk_tok_fetch_groups', 'wk_tok_strata_clear',
     'wk_tok_strata_load', 'wk_tok_strata_labels', 'wk_tok_strata_select',
@@ -269,6 +270,9 @@ def load_library():
         'wk_dtok_stage_reads': (C.c_int, [p, i64p, i64p, C.POINTER(C.c_int)]),
         'wk_demux_fetch': (C.c_int, [p, i32p, C.c_int64, C.c_void_p,
                                      C.c_int32]),
+        'wk_dtok_stage_reads_strata': (C.c_int, [p, i64p, i64p,
+                                                 C.POINTER(C.c_int)]),
+        'wk_chunk_groups': (C.c_int, [p, i32p, C.c_int64]),
         'wk_tok_subjects': (C.c_int, [p, i32p, i32p, i64p]),
         'wk_tok_new_subjects': (C.c_int, [p, C.c_char_p, i32p]),
         'wk_tok_fetch_groups': (C.c_int, [p, i32p]),
@@ -1082,6 +1086,27 @@ class Context:
             0 if group is None else group.size,
             C.c_void_p(met.ctypes.data) if met.size else None, met.size))
         return met, group
+
+    # -- plain classification with a strata map (csrc/wk_strata_reads.hpp) --
+    def dtok_stage_reads_strata(self):
+        """The scanned block (plain flavour; behind ``strata_load`` and
+        ``strata_groups``, demultiplexing off) as the staged classify chunk:
+        a read's group is its label's, -1 for a read the map does not hold.
+        Returns (status, reads, records); status != 0: the host tokenizer
+        takes the block."""
+        a, b, st = C.c_int64(0), C.c_int64(0), C.c_int(1)
+        self._check(self._lib.wk_dtok_stage_reads_strata(
+            self._h, C.byref(a), C.byref(b), C.byref(st)))
+        return st.value, a.value, b.value
+
+    def chunk_groups(self, n_reads):
+        """The groups of the ``n_reads`` reads of the chunk that
+        ``dtok_stage_reads`` / ``dtok_stage_reads_strata`` staged last."""
+        group = np.empty(n_reads, dtype=np.int32)
+        self._check(self._lib.wk_chunk_groups(
+            self._h, _ptr(group, C.c_int32) if group.size else None,
+            group.size))
+        return group
 
     def ordinal_hit_offsets(self, n_hits):
         """Offsets of every hit's genes in the staged gene lists

@@ -78,6 +78,31 @@ def demux_on_device(native_demux, fmt, coords=False, sizes=False, n_jobs=1,
                 and 1 <= n_jobs <= nat.MAX_JOBS)
 
 
+def strata_reads_on_device(fmt, strata=True, demux=False, coords=False,
+                           sizes=False, outmap=False, outcov=False, part=None,
+                           n_jobs=1, replay=False, own_text=True):
+    """Does a file of plain classification under `--stratify` keep the device
+    text route, the stratum of every read joined on the device
+    (csrc/wk_strata_reads.hpp, `_run_dstrata_reads`)?  A strata map
+    (``strata``) without `--demux`, not ``coords`` (that join is
+    `_run_dhits`'); SAM, BLAST tabular, PAF or simple-map text that can be
+    read block by block (``own_text``: a plain file or a gzip file this
+    package inflates itself -- not stdin, not bzip2 / xz); the whole file
+    (``part``); with or without `--trim-sub` / `--exclude`; any job set of at
+    most `MAX_JOBS` jobs (``n_jobs``).  Not with read maps (``outmap``),
+    subject coverage (``outcov``) or `--sizes`, and not during the replay
+    pass (``replay``: it wants the assignments on the host).
+    ``WOLTKA_NO_DSTRATA=1`` (like ``WOLTKA_NO_DTOK=1``) keeps every file on
+    the host route."""
+    if os.environ.get('WOLTKA_NO_DSTRATA') or os.environ.get('WOLTKA_NO_DTOK'):
+        return False
+    return bool(strata and not demux and not coords and not sizes
+                and not outmap and not outcov and not replay
+                and part is None and own_text
+                and fmt in ('sam', 'b6o', 'paf', 'map')
+                and 1 <= n_jobs <= nat.MAX_JOBS)
+
+
 class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
              Folding):
     """One classification job on one GPU.
@@ -224,6 +249,7 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
         self._mring = None          # pinned buffers the map text is fetched into
         # strata map joined on the device (csrc/wk_strata.hpp)
         self._dstrata = None        # {'fp', 'labels', 'slots', 'key'} while the device holds the sample's map
+        self._dreads = False        # plain classification of the file is joined with it there (csrc/wk_strata_reads.hpp)
         self._sbuf = [None, None]   # pinned buffers the map text is inflated into
         self._sbuf_next = 0
 
@@ -387,7 +413,7 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
                       want_strings=True, want_samples=False, cover=None,
                       fmt='sam', part=None, words=False, dmaps=None,
                       keep_empty=False, words_dev=False, dcover=False,
-                      ddemux=None):
+                      ddemux=None, dreads=False):
         """SAM text -> packed chunks through the native tokenizer.  Yields
         (reads or None, packed, strata ids, name descriptors, sample ids,
         ranges) where packed = (subj, qoff) of subject indices, or for
@@ -401,7 +427,10 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
         (`regroup_hits` counts them where ordinal.py:222 does, then drops
         them).  ``ddemux`` (`demux_on_device`): (whitelist or None,) -- the
         samples are told on the device and the blocks counted as CSR chunks
-        there (`_run_ddemux`)."""
+        there (`_run_ddemux`).  ``dreads`` (`strata_reads_on_device`): plain
+        classification with ``want_groups`` -- while the device holds the
+        sample's strata map the reads' strata are joined there and the blocks
+        counted as CSR chunks (`_run_dstrata_reads`)."""
         from .align import native_sam_blocks
         if self.tok is None:
             # (a tokenizer whose dictionary was filled from this file's first
@@ -426,12 +455,17 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
         dcover = bool(dcover and cover is not None and not ordinal)
         ddemux = ddemux if (ddemux is not None and want_samples and
                             not ordinal and cover is None) else None
+        # (a map the device refused leaves the sample on the host route)
+        dreads = bool(dreads and want_groups and self._dstrata is not None
+                      and not ordinal and cover is None and not want_names
+                      and not want_samples and part is None
+                      and len(self.jobs) <= nat.MAX_JOBS)
         if (words or words_dev or device_ex or dmaps or dcover or
-                ddemux is not None) and (
+                ddemux is not None or dreads) and (
                 fmt in ('sam', 'b6o', 'paf') or (fmt == 'map' and
                                                  not ordinal)) and \
-                (not exclude or ((words or words_dev or ddemux is not None)
-                                 and not dmaps)) and \
+                (not exclude or ((words or words_dev or ddemux is not None
+                                  or dreads) and not dmaps)) and \
                 not os.environ.get('WOLTKA_NO_DTOK'):
             from .align import _parallel_reader, part_range
             from .file import GunzipStream
@@ -457,15 +491,17 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
                     else None
                 self._dcover = cover if dcover else None
                 self._ddemux = ddemux
-                if ddemux is not None:
+                self._dreads = dreads
+                if ddemux is not None or dreads:
                     # (the reader started before the hierarchy was read is
-                    # not taken under `--demux`: the engine's own reader, as
-                    # for a file whose turn has come)
+                    # not taken under `--demux` or with a strata map: the
+                    # engine's own reader, as for a file whose turn has come)
                     from .routes.device_text import drop_text_ahead
                     drop_text_ahead()
                     # (six kernels and a lookup per block: neither the
                     # one-kernel tokenizer nor scan and emission in one wait)
                     self._spec = False
+                if ddemux is not None:
                     self._dx_full = False
                     if self._dx_names is None:
                         self.ctx.demux_begin(True)
@@ -493,6 +529,7 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
                     self._dmaps = None
                     self._dcover = None
                     self._ddemux = None
+                    self._dreads = False
                     if getattr(self.ctx, '_h', None):   # (still open)
                         self.ctx.dtok_keep_reads(False)
                 return
@@ -722,6 +759,7 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
                 'dcover': '_run_dcover',    # ... for the "ex" parsers under `--outcov`: ranges to the coverage pile, then the same
                 'dhits': '_run_dhits',      # text scanned on the device -> coord-match hits
                 'ddemux': '_run_ddemux',    # text scanned on the device -> demultiplexed CSR chunk, counted by the general evaluator
+                'dreads': '_run_dstrata_reads',     # ... -> CSR chunk with the reads' strata joined on the device, counted likewise
                 'words': '_run_words'}      # packed records of the host tokenizer (routes/words.py)
 
     def _run_general(self, data, reads, subque, sample_of, strata_of, trimsub,

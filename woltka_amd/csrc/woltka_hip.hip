@@ -24,6 +24,7 @@
 #include "wk_device.hpp"
 #include "wk_dtok.hpp"
 #include "wk_demux.hpp"
+#include "wk_strata_reads.hpp"
 #include "wk_dtok_fused.hpp"
 #include "wk_free.hpp"
 #include "wk_ordinal.hpp"
@@ -445,7 +446,7 @@ struct wk_ctx {
     bool dx_looked = false;               // wk_demux_pending has looked the scanned block's samples up
     bool dx_runs = false;                 // ... and its run starts are told, its subject map and exclusion set applied
     int dx_status = 1;                    // ... and what it found
-    bool dx_chunk = false;                // the staged chunk is wk_dtok_stage_reads'
+    bool dx_chunk = false;                // the staged chunk is wk_dtok_stage_reads' or wk_dtok_stage_reads_strata's
     int32_t dx_groups_n = 0;              // samples that have a group (wk_demux_register)
     uint64_t dx_hash_mask = 0;            // (tests) option "demux_hash_mask"
     int64_t dx_max_opt = 0;               // (tests) option "demux_max_samples"
@@ -5084,8 +5085,27 @@ int wk_demux_begin(wk_ctx* c, int on) {
     return WK_OK;
 }
 
-// run starts, subject map and exclusion set of the scanned block (as dtok_emit_launch has them), then the lookup of its
-// reads' samples; the pending names end up in dx_pend_*
+// run starts, subject map and exclusion set of the scanned block (as dtok_emit_launch has them), queued once per scanned
+// block: the runs are told with every mapped line in place -- a run the exclusion set drops still separates its
+// neighbours
+static int reads_runs_once(wk_ctx* c, const DtokArgs& a, dim3 grid) {
+    if (c->dx_runs) return WK_OK;
+    hipLaunchKernelGGL(dtok_runs_kernel, grid, dim3(kDtokThreads), 0, c->stream, a);
+    if (a.submap && !c->dt_mapped) {
+        hipLaunchKernelGGL(dtok_submap_kernel, grid, dim3(kDtokThreads), 0, c->stream, a);
+        if (c->dt_has_excl) {
+            HIP_TRY(c, hipMemsetAsync(c->d_first.p, 0, c->dt_lines, c->stream));
+            hipLaunchKernelGGL(dtok_excl_mark_kernel, grid, dim3(kDtokThreads), 0, c->stream, a);
+            hipLaunchKernelGGL(dtok_excl_drop_kernel, grid, dim3(kDtokThreads), 0, c->stream, a);
+        }
+        c->dt_mapped = true;
+    }
+    c->dx_runs = true;
+    return WK_OK;
+}
+
+// run starts, subject map and exclusion set of the scanned block, then the lookup of its reads' samples; the pending
+// names end up in dx_pend_*
 static int demux_lookup(wk_ctx* c) {
     c->dx_pend_off.clear();
     c->dx_pend_len.clear();
@@ -5106,20 +5126,9 @@ static int demux_lookup(wk_ctx* c) {
     const DemuxArgs d = demux_args(c);
     const dim3 grid((lines + kDtokThreads - 1) / kDtokThreads);
     KernelTimer* kt = ktimer_begin(c, "demux_lookup");
-    // (once per scanned block: the runs are told with every mapped line in place -- a run the exclusion set drops still
-    // separates its neighbours)
-    if (!c->dx_runs) {
-        hipLaunchKernelGGL(dtok_runs_kernel, grid, dim3(kDtokThreads), 0, c->stream, a);
-        if (a.submap && !c->dt_mapped) {
-            hipLaunchKernelGGL(dtok_submap_kernel, grid, dim3(kDtokThreads), 0, c->stream, a);
-            if (c->dt_has_excl) {
-                HIP_TRY(c, hipMemsetAsync(c->d_first.p, 0, lines, c->stream));
-                hipLaunchKernelGGL(dtok_excl_mark_kernel, grid, dim3(kDtokThreads), 0, c->stream, a);
-                hipLaunchKernelGGL(dtok_excl_drop_kernel, grid, dim3(kDtokThreads), 0, c->stream, a);
-            }
-            c->dt_mapped = true;
-        }
-        c->dx_runs = true;
+    {
+        const int rc = reads_runs_once(c, a, grid);
+        if (rc) return rc;
     }
     hipLaunchKernelGGL(demux_lookup_kernel, grid, dim3(kDtokThreads), 0, c->stream, a, d);
     hipLaunchKernelGGL(demux_verify_kernel, grid, dim3(kDtokThreads), 0, c->stream, a, d);
@@ -5258,6 +5267,8 @@ int wk_demux_register(wk_ctx* c, const char* blob, const int64_t* off, int32_t n
     return WK_OK;
 }
 
+static int stage_reads_chunk(wk_ctx* c, bool strata, int64_t* n_reads, int64_t* n_records, int* status);
+
 int wk_dtok_stage_reads(wk_ctx* c, int64_t* n_reads, int64_t* n_records, int* status) {
     if (!c || !n_reads || !n_records || !status) return WK_E_ARG;
     *status = 1;
@@ -5280,12 +5291,19 @@ int wk_dtok_stage_reads(wk_ctx* c, int64_t* n_reads, int64_t* n_records, int* st
         }
         if (!c->dx_pend_off.empty()) return fail(c, WK_E_STATE, "the block brings samples the table does not hold (wk_demux_pending, wk_demux_register)");
     }
+    return stage_reads_chunk(c, false, n_reads, n_records, status);
+}
+
+// The block scanned last for the plain flavour as the staged CSR chunk with a group per read: the group of the read's
+// sample (wk_demux.hpp; the samples have been looked up) or, `strata`, of its stratum in the map that is loaded
+// (wk_strata_reads.hpp).  *status stays 1 for a block the kernels leave to the host tokenizer.
+static int stage_reads_chunk(wk_ctx* c, bool strata, int64_t* n_reads, int64_t* n_records, int* status) {
     c->dt_ready = false;
     c->dx_looked = false;
     c->chunk_valid = false;
     c->dx_chunk = false;
     const uint32_t lines = c->dt_lines;
-    const size_t n_samples = c->dx_name_off_host.size();
+    const size_t n_samples = strata ? 0 : c->dx_name_off_host.size();
     if (n_samples) HIP_TRY(c, hipMemsetAsync(c->dx_met.p, 0, n_samples, c->stream));
     unsigned long long totals = 0;
     uint32_t st[4] = {0, 0, 0, 0};
@@ -5295,37 +5313,47 @@ int wk_dtok_stage_reads(wk_ctx* c, int64_t* n_reads, int64_t* n_records, int* st
     HIP_TRY(c, c->c_group.reserve(((size_t)lines + 1) * 4));
     if (lines > 0) {
         DtokArgs a = dtok_args(c);
-        DemuxArgs d = demux_args(c);
-        d.c_subj = c->c_subj.as<int32_t>();
-        d.c_qoff = c->c_qoff.as<int32_t>();
-        d.c_group = c->c_group.as<int32_t>();
-        d.cap = lines;
         const uint32_t n_tiles = (lines + kDtokThreads - 1) / kDtokThreads;
         HIP_TRY(c, c->d_tiles.reserve((size_t)n_tiles * 8));
         HIP_TRY(c, c->d_tile_off.reserve((size_t)n_tiles * 8));
         HIP_TRY(c, c->d_lscan.reserve(((size_t)lines + 1) * 8));
         a.line_scan = c->d_lscan.as<unsigned long long>();
         HIP_TRY(c, hipMemsetAsync(scalar_u64(c, 3), 0, 8, c->stream));
-        HIP_TRY(c, hipMemsetAsync(c->dx_state.p, 0, 16, c->stream));
+        if (!strata) HIP_TRY(c, hipMemsetAsync(c->dx_state.p, 0, 16, c->stream));
         const dim3 grid(n_tiles);
-        KernelTimer* kt = ktimer_begin(c, "demux_stage");
+        KernelTimer* kt = ktimer_begin(c, strata ? "strata_stage" : "demux_stage");
+        if (strata) {  // (under `--demux` the lookup of the samples has told the runs)
+            const int rc = reads_runs_once(c, a, grid);
+            if (rc) return rc;
+        }
         hipLaunchKernelGGL(dtok_first_kernel, grid, dim3(kDtokThreads), 0, c->stream, a);
         hipLaunchKernelGGL(dtok_hits_kernel<false>, grid, dim3(kDtokThreads), 0, c->stream, a, c->d_tiles.as<unsigned long long>());
         hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_tiles.as<unsigned long long>(),
                            c->d_tile_off.as<unsigned long long>(), (int64_t)n_tiles, scalar_u64(c, 3));
         hipLaunchKernelGGL(dtok_scan_lines_kernel, grid, dim3(kDtokThreads), 0, c->stream, a, c->d_tile_off.as<unsigned long long>());
-        hipLaunchKernelGGL(demux_place_reads_kernel, grid, dim3(kDtokThreads), 0, c->stream, a, d);
+        if (strata) {
+            const StrataChunk ch{c->c_subj.as<int32_t>(), c->c_qoff.as<int32_t>(), c->c_group.as<int32_t>(), lines};
+            hipLaunchKernelGGL(strata_place_reads_kernel, grid, dim3(kDtokThreads), 0, c->stream, a, strata_args(c), ch);
+        } else {
+            DemuxArgs d = demux_args(c);
+            d.c_subj = c->c_subj.as<int32_t>();
+            d.c_qoff = c->c_qoff.as<int32_t>();
+            d.c_group = c->c_group.as<int32_t>();
+            d.cap = lines;
+            hipLaunchKernelGGL(demux_place_reads_kernel, grid, dim3(kDtokThreads), 0, c->stream, a, d);
+        }
         ktimer_end(c, kt);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, small_back(c, 0, c->d_state.p, sizeof ds));
         HIP_TRY(c, small_back(c, 1, scalar_u64(c, 3), 8));
-        HIP_TRY(c, small_back(c, 2, c->dx_state.p, 16));
+        if (!strata) HIP_TRY(c, small_back(c, 2, c->dx_state.p, 16));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         small_back_get(c, 0, &ds, sizeof ds);
         small_back_get(c, 1, &totals, 8);
-        small_back_get(c, 2, st, 16);
+        if (!strata) small_back_get(c, 2, st, 16);
     }
-    if (ds.flags || st[0]) return WK_OK;  // (a read of more than WK_MAX_K subjects: the host tokenizer's block)
+    // (a read of more than WK_MAX_K subjects, a name the host has not mapped: the host tokenizer's block)
+    if (ds.flags || st[0]) return WK_OK;
     const int64_t records = (int64_t)(totals & 0xFFFFFFFFull), reads = (int64_t)(totals >> 32);
     if (records > (int64_t)lines || reads > records) return fail(c, WK_E_STATE, "the block's reads do not add up");
     // (the offsets' last entry; the stream orders it in front of whatever reads them)
@@ -5358,6 +5386,31 @@ int wk_demux_fetch(wk_ctx* c, int32_t* group, int64_t group_cap, unsigned char* 
     DeviceGuard guard(c->device);
     if (group && c->n_reads) HIP_TRY(c, hipMemcpyAsync(group, c->c_group.p, (size_t)c->n_reads * 4, hipMemcpyDeviceToHost, c->stream));
     if (met && n_samples) HIP_TRY(c, hipMemcpyAsync(met, c->dx_met.p, n_samples, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return WK_OK;
+}
+
+// ---- plain classification with a strata map on the device (wk_strata_reads.hpp) -------------------------------------
+
+int wk_dtok_stage_reads_strata(wk_ctx* c, int64_t* n_reads, int64_t* n_records, int* status) {
+    if (!c || !n_reads || !n_records || !status) return WK_E_ARG;
+    *status = 1;
+    *n_reads = *n_records = 0;
+    if (!c->s_ready || !c->s_use) return fail(c, WK_E_STATE, "no strata map with groups on the device (wk_strata_load, wk_strata_groups)");
+    if (c->dx_on) return fail(c, WK_E_STATE, "the reads' groups are their samples' (wk_demux_begin): wk_dtok_stage_reads");
+    if (!c->dt_ready || c->dt_extra) return fail(c, WK_E_STATE, "no block scanned for the plain flavour (wk_dtok_scan)");
+    if (c->acc_open) return fail(c, WK_E_STATE, "staged hits not counted yet (wk_ordinal_count)");
+    DeviceGuard guard(c->device);
+    KtScope kt_scope(c);
+    return stage_reads_chunk(c, true, n_reads, n_records, status);
+}
+
+int wk_chunk_groups(wk_ctx* c, int32_t* group, int64_t cap) {
+    if (!c || cap < 0 || (cap > 0 && !group)) return WK_E_ARG;
+    if (!c->dx_chunk || !c->chunk_valid) return fail(c, WK_E_STATE, "no chunk staged by wk_dtok_stage_reads / wk_dtok_stage_reads_strata");
+    if (cap < c->n_reads) return fail(c, WK_E_CAPACITY, "need room for %lld groups", (long long)c->n_reads);
+    DeviceGuard guard(c->device);
+    if (c->n_reads) HIP_TRY(c, hipMemcpyAsync(group, c->c_group.p, (size_t)c->n_reads * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return WK_OK;
 }

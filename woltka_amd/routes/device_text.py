@@ -3,7 +3,8 @@ into pinned memory, scanned, and appended as packed records (`_run_dtok`) or
 staged as coord-match hits (`_run_dhits`) or, demultiplexed there
 (csrc/wk_demux.hpp), as CSR chunks with a group per read (`_run_ddemux`); read
 maps formatted there (csrc/wk_readmap.hpp) and the strata map joined there
-(csrc/wk_strata.hpp).
+(csrc/wk_strata.hpp) -- with the hits of the coord-match, or with the reads of
+plain classification (csrc/wk_strata_reads.hpp, `_run_dstrata_reads`).
 Blocks the kernels leave alone go through the host tokenizer (`_host_block`)."""
 import os
 import time
@@ -1149,7 +1150,8 @@ class DeviceTextRoute:
             try:
                 t0 = time.perf_counter()
                 done = None
-                if self._spec and not ex and self._ddemux is None:
+                if self._spec and not ex and self._ddemux is None and \
+                        not self._dreads:
                     # (the sample's words are open and the block before went
                     # through: scan and emission with one wait)
                     status, n_lines, done = self.ctx.dtok_scan_emit(
@@ -1198,6 +1200,10 @@ class DeviceTextRoute:
                         yield None, ('ddemux', (text, fill, first, final,
                                                 hdr_in, hdr, n_lines)), \
                             None, None, None, None
+                    elif n_lines and self._dreads:
+                        yield None, ('dreads', (text, fill, first, final,
+                                                hdr_in, hdr, n_lines)), \
+                            None, None, None, None
                     elif n_lines:
                         yield None, ('dcover' if cover else 'dtok', (
                             text, fill, first, final, hdr_in, hdr, done)), \
@@ -1209,7 +1215,8 @@ class DeviceTextRoute:
                                                 hdr_in,
                                                 names=self._dmaps is not None,
                                                 cover=cover,
-                                                samples=self._ddemux is not None)
+                                                samples=self._ddemux is not None,
+                                                groups=self._dreads)
             finally:
                 # (a block in a ring buffer: the reader took the buffer back
                 # when its copy was through)
@@ -1230,7 +1237,7 @@ class DeviceTextRoute:
             # one-kernel tokenizer: no newline count behind a block's copy)
             self.ctx.set_option('dtok_count_ahead', int(bool(
                 ex or self._dmaps is not None or self._dfmt != 'sam' or
-                self._ddemux is not None)))
+                self._ddemux is not None or self._dreads)))
         ahead, whole = taken, None
         if ahead is None:
             whole = open_mapped() if source is None else None
@@ -1304,7 +1311,7 @@ class DeviceTextRoute:
                     break
                 slot = item[0]
                 if may_lag and self._spec and self._dmaps is None and \
-                        self._ddemux is None and \
+                        self._ddemux is None and not self._dreads and \
                         isinstance(slot, tuple) and slot[0] == 'det':
                     t0 = time.perf_counter()
                     begun = self.ctx.dtok_scan_emit_begin(tok, item[1],
@@ -1415,7 +1422,9 @@ class DeviceTextRoute:
         names, for the read maps; ``cover``: the "ex" parsers' records with
         their ranges (coverage subject id, beg, end) as the last item;
         ``samples``: with the reads' sample ids, numbered like
-        `_tok_samples`, as the fifth item)."""
+        `_tok_samples`, as the fifth item; ``groups``: with the reads' strata,
+        joined on the host and numbered like the device's labels, as the
+        third item)."""
         ROUTES['host_block'] += 1
         if isinstance(buf, _BlockText):     # (the bytes come back from the device)
             buf = buf.get()
@@ -1446,9 +1455,12 @@ class DeviceTextRoute:
                     (self._host_strata_ids(res['group']) if groups else None), \
                     None, None, None
             return
+        if groups:      # (the join of this block on the host)
+            self._host_strata_table()
         res = tok.parse(memoryview(buf).cast('B')[:fill], first=first,
                         final=final, fmt=self._dfmt, want_names=names,
-                        extra=3 if cover else False, want_samples=samples)
+                        extra=3 if cover else False, want_samples=samples,
+                        want_groups=groups)
         if samples:
             self._tok_samples.extend(tok.new_samples())
         fresh = tok.new_subjects()
@@ -1459,7 +1471,8 @@ class DeviceTextRoute:
         if res['off'].size > 1:
             subj = res['subj'] if self._tok_identity \
                 else self._tok_map[res['subj']]
-            yield None, (subj, res['off']), None, \
+            yield None, (subj, res['off']), \
+                (self._host_strata_ids(res['group']) if groups else None), \
                 ((buf[:fill], res['qname']) if names else None), \
                 (res['sample'] if samples else None), \
                 ((self._tok_cover[res['subj']], res['beg'], res['end'])
@@ -1710,6 +1723,42 @@ class DeviceTextRoute:
             n += self.run_chunk(data, None, None, None, None, None, None,
                                 None, None, False, packed=(subj, qoff),
                                 sample_ids=ids, allow=allow,
+                                packed_is_set=not self._dtrimsub)
+        self.tok.set_header_state(hdr)
+        return n
+
+    def _run_dstrata_reads(self, data, packed, sample):
+        """A block the device has scanned for plain classification while it
+        holds the sample's strata map: the block is staged as a CSR chunk
+        whose reads carry the group of their stratum, -1 for a read the map
+        does not hold (`wk_dtok_stage_reads_strata`), and counted by the
+        general evaluator.  A block the kernels refuse -- a read of more
+        subjects than a count key can say -- goes through the host tokenizer
+        with the host's join."""
+        buf, fill, first, final, hdr_in, hdr, n_lines = packed[1]
+        ds = self._dstrata
+        self._sync_subjects(data)
+        # room for the groups and the count keys the block can add (before
+        # its groups are taken: a fold numbers them anew)
+        if len(self.groups) + len(ds['labels']) + 1 >= MAX_GROUPS // 2:
+            self.collect(data)
+        self._ensure_table(data, n_lines, min(n_lines, len(ds['labels']) + 1))
+        self._device_strata_groups(sample)
+        status, n_reads, _ = self.ctx.dtok_stage_reads_strata()
+        if status == 0:
+            ROUTES['dreads_strata'] += 1
+            if n_reads:
+                for rank in self.ranks:
+                    data[rank].setdefault(sample, {})
+                self._classify_staged(data, False)
+            self._n_reads += n_reads
+            return n_reads
+        n = 0
+        for _, (subj, qoff), ids, *_ in self._host_block(
+                buf, fill, first, final, hdr_in, groups=True):
+            n += self.run_chunk(data, None, None, sample, None, None, None,
+                                None, None, False, packed=(subj, qoff),
+                                strata_ids=ids, strata_labels=ds['labels'],
                                 packed_is_set=not self._dtrimsub)
         self.tok.set_header_state(hdr)
         return n

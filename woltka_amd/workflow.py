@@ -25,7 +25,7 @@ import numpy as np
 
 from .align import NATIVE_FORMATS, infer_align_format, plain_mapper
 from .classify import (Engine, cover_on_device, demux_on_device,
-                       exact_to_numbers)
+                       exact_to_numbers, strata_reads_on_device)
 from .file import (FilesAhead, id2file_from_dir, id2file_from_map, openzip, path2stem,
                    read_ids, read_map_1st, read_map_uniq, readzip, readzip_bytes,
                    stem2rank, write_readmap)
@@ -424,8 +424,27 @@ def classify(
                     want_names = bool((demux and not native_demux) or
                                       rank2dir is not None or
                                       (stratmap and not (native and native_strata)))
+                    dreads = False
                     if native:
                         if native_strata:
+                            # (text the device route can read block by
+                            # block: a plain file, or a gzip file this
+                            # package inflates itself)
+                            from .file import ZIP_BY_EXT, GunzipStream
+                            from os.path import splitext
+                            own_text = path != '-' and (
+                                ZIP_BY_EXT.get(splitext(path)[1]) is None
+                                or isinstance(stream, GunzipStream))
+                            # plain classification: the reads' strata are
+                            # joined on the device (csrc/wk_strata_reads.hpp)
+                            dreads = strata_reads_on_device(
+                                fmt_, strata=True, demux=bool(demux),
+                                coords=bool(ordinal), sizes=bool(sizes),
+                                outmap=rank2dir is not None,
+                                outcov=cover is not None, part=part,
+                                n_jobs=len(engine.jobs),
+                                replay=engine._replay is not None,
+                                own_text=own_text)
                             sample = files[fp] if files else None
                             if sample != csample or labels is None:
                                 # (the map of the sample after this one is
@@ -436,20 +455,16 @@ def classify(
                                 # coord-match on text that the device tokenises
                                 # (SAM, BLAST tabular, PAF): the join runs
                                 # there too
-                                from .file import ZIP_BY_EXT, GunzipStream
-                                from os.path import splitext
                                 dstrata = bool(
                                     ordinal and fmt_ in ('sam', 'b6o', 'paf')
                                     and not exclude
                                     and part is None and cover is None and
-                                    rank2dir is None and path != '-' and
-                                    (ZIP_BY_EXT.get(splitext(path)[1]) is None
-                                     or isinstance(stream, GunzipStream))
+                                    rank2dir is None and own_text
                                     and not os.environ.get('WOLTKA_NO_DTOK'))
                                 labels = engine.load_strata(
                                     stratmap[sample], zippers,
                                     then=stratmap[later[0]] if later else None,
-                                    device=dstrata)
+                                    device=dstrata or dreads)
                                 csample = sample
                         # read ids as Python strings only when the host logic
                         # needs them (demultiplexing, Python-side strata join);
@@ -513,7 +528,8 @@ def classify(
                             ddemux=(allow,) if demux_on_device(
                                 native_demux, fmt_, coords=bool(ordinal),
                                 sizes=bool(sizes), n_jobs=len(engine.jobs),
-                                replay=engine._replay is not None) else None)
+                                replay=engine._replay is not None) else None,
+                            dreads=dreads)
                         if ordinal and rank2dir is not None:
                             chunks = engine.regroup_hits(chunks, n)
                     else:
