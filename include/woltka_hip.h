@@ -548,7 +548,11 @@ int wk_dtok_stage_hits_append(wk_ctx* ctx, const int32_t* genome_of_subject,
  *   wk_demux_pending   behind a wk_dtok_scan of the plain flavour (status 0):
  *                      run starts, the subject map and the exclusion set
  *                      (wk_dtok_subject_map), then the lookup of every
- *                      emitted read's sample.  *n = the samples the table does
+ *                      emitted read's sample.  Behind a scan of the "ex"
+ *                      flavour: run starts, then the lookup of the sample of
+ *                      every read that has a hit -- a mapped line of aligned
+ *                      length > 0 (ordinal.py:231); wk_dtok_stage_hits_demux
+ *                      follows.  *n = the samples the table does
  *                      not hold yet, *n_bytes = the bytes of their names.
  *                      With off / len / blob given (cap >= *n, blob_cap >=
  *                      *n_bytes) a second call copies them out: in order of
@@ -567,9 +571,26 @@ int wk_dtok_stage_hits_append(wk_ctx* ctx, const int32_t* genome_of_subject,
  *                      yields them; wk_classify_staged follows.  *status != 0:
  *                      nothing is staged, the host tokenizer takes the block
  *                      (a read of more than WK_MAX_K subjects).
+ *   wk_dtok_stage_hits_demux  coord-match under demultiplexing: behind a
+ *                      wk_dtok_scan of the "ex" flavour (status 0) with
+ *                      wk_demux_begin(1) in force, the block's hits as the
+ *                      staged chunk of the coord-match (what wk_dtok_stage_hits
+ *                      leaves) with a group per read: its sample's, -1 outside
+ *                      the whitelist.  Refuses (WK_E_STATE) while names are
+ *                      pending or samples have no group.  *status != 0: nothing
+ *                      is staged, the host tokenizer takes the block (more
+ *                      samples than the table holds, a name the table does
+ *                      not hold, a flag the scan raised).  wk_ordinal_count or
+ *                      wk_ordinal_match + wk_classify_staged follow; the
+ *                      match marks the samples met.
  *   wk_demux_fetch     group[0, n_reads) of the chunk staged last (null: not
  *                      wanted) and met[0, n_samples): 1 for every sample that
- *                      a read of that chunk with a group belongs to.
+ *                      a read of that chunk with a group belongs to.  Behind
+ *                      wk_dtok_stage_hits_demux and the match (wk_ordinal_match,
+ *                      wk_ordinal_count): the reads are the block's reads with
+ *                      a hit, and a sample is met when such a read with a
+ *                      group matched a gene -- the reads workflow.demultiplex
+ *                      sees behind ordinal_mapper (workflow.py:304-335).
  * wk_set_option "demux_hash_mask" (AND-ed into every hash, 0: none) and
  * "demux_max_samples" (0: 65536) are for tests; set them before
  * wk_demux_begin. */
@@ -581,6 +602,9 @@ int wk_demux_register(wk_ctx* ctx, const char* blob, const int64_t* off,
                       int32_t n, const int32_t* group, int32_t n_total);
 int wk_dtok_stage_reads(wk_ctx* ctx, int64_t* n_reads, int64_t* n_records,
                         int* status);
+int wk_dtok_stage_hits_demux(wk_ctx* ctx, const int32_t* genome_of_subject,
+                             int32_t n_subjects, double th, int64_t* n_reads,
+                             int64_t* n_hits, int* status);
 int wk_demux_fetch(wk_ctx* ctx, int32_t* group, int64_t group_cap,
                    unsigned char* met, int32_t met_cap);
 

@@ -64,7 +64,7 @@ SYMBOLS = (
     'wk_dtok_readmap_fetch', 'wk_strata_load', 'wk_strata_labels',
     'wk_strata_groups', 'wk_strata_clear',
     'wk_demux_begin', 'wk_demux_pending', 'wk_demux_register',
-    'wk_dtok_stage_reads', 'wk_demux_fetch',
+    'wk_dtok_stage_reads', 'wk_demux_fetch', 'wk_dtok_stage_hits_demux',
     'wk_dtok_stage_reads_strata', 'wk_chunk_groups',
     'wk_tok_subjects',
     'wk_tok_new_subjects', 'wk_tok_fetch_groups', 'wk_tok_strata_clear',
@@ -261,6 +261,9 @@ def load_library():
         'wk_strata_labels': (C.c_int, [p, i32p, i64p, i32p, C.c_int32, i32p]),
         'wk_strata_groups': (C.c_int, [p, i32p, i32p, C.c_int32]),
         'wk_strata_clear': (C.c_int, [p]),
+        'wk_dtok_stage_hits_demux': (C.c_int, [p, i32p, C.c_int32, C.c_double,
+                                               i64p, i64p,
+                                               C.POINTER(C.c_int)]),
         'wk_demux_begin': (C.c_int, [p, C.c_int]),
         'wk_demux_pending': (C.c_int, [p, i64p, i32p, C.c_int32, i32p,
                                        C.c_void_p, C.c_int64, i64p,
@@ -1033,12 +1036,14 @@ class Context:
     # -- demultiplexing on the device (csrc/wk_demux.hpp) -------------------
     def demux_begin(self, on=True):
         """Clear the device's sample table; ``on``: blocks of the plain
-        flavour may be staged by ``dtok_stage_reads`` from now on."""
+        flavour may be staged by ``dtok_stage_reads``, blocks of the "ex"
+        flavour by ``dtok_stage_hits_demux`` from now on."""
         self._check(self._lib.wk_demux_begin(self._h, int(bool(on))))
 
     def demux_pending(self):
         """The samples of the block scanned last that the table does not
-        hold yet.  Returns (status, names as bytes in order of the first read
+        hold yet (behind a scan of the "ex" flavour: of its reads that have a
+        hit).  Returns (status, names as bytes in order of the first read
         that brought them); status != 0: the host tokenizer takes the block
         (bit 0: more samples than the table holds)."""
         n, nb, st = C.c_int32(0), C.c_int64(0), C.c_int(1)
@@ -1074,6 +1079,18 @@ class Context:
         a, b, st = C.c_int64(0), C.c_int64(0), C.c_int(1)
         self._check(self._lib.wk_dtok_stage_reads(
             self._h, C.byref(a), C.byref(b), C.byref(st)))
+        return st.value, a.value, b.value
+
+    def dtok_stage_hits_demux(self, genome_of_subject, th):
+        """The scanned block's hits ("ex" flavour, behind ``demux_pending``)
+        as the staged coord-match chunk with a group per read: its sample's.
+        Returns (status, reads, hits); status != 0: the host tokenizer takes
+        the block."""
+        g = _arr(genome_of_subject, np.int32)
+        a, b, st = C.c_int64(0), C.c_int64(0), C.c_int(1)
+        self._check(self._lib.wk_dtok_stage_hits_demux(
+            self._h, _ptr(g, C.c_int32), g.size, float(th), C.byref(a),
+            C.byref(b), C.byref(st)))
         return st.value, a.value, b.value
 
     def demux_fetch(self, n_samples, n_reads=None):

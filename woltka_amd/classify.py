@@ -78,6 +78,25 @@ def demux_on_device(native_demux, fmt, coords=False, sizes=False, n_jobs=1,
                 and 1 <= n_jobs <= nat.MAX_JOBS)
 
 
+def demux_hits_on_device(native_demux, fmt, sizes=False, exclude=False,
+                         n_jobs=1, replay=False):
+    """Does a file of the coord-match (`--coords`) that is demultiplexed keep
+    the device text route, the sample of every read decided on the device
+    and the hits staged with a group per read (csrc/wk_demux.hpp,
+    `_run_dhits_demux`)?  ``native_demux``: `--demux` (or a single-file
+    input) without a strata map, read maps or subject coverage; SAM, BLAST
+    tabular or PAF text; with or without `--sizes` (``sizes``: the
+    contribution log takes it); not with `--exclude` (the "ex" parsers' way
+    with it stays the host's); any job set of at most `MAX_JOBS` jobs
+    (``n_jobs``); not during the replay pass.  ``WOLTKA_NO_DDEMUX=1`` (like
+    ``WOLTKA_NO_DTOK=1``) keeps every file on the host route."""
+    if os.environ.get('WOLTKA_NO_DDEMUX') or os.environ.get('WOLTKA_NO_DTOK'):
+        return False
+    return bool(native_demux and not exclude and not replay
+                and fmt in ('sam', 'b6o', 'paf')
+                and 1 <= n_jobs <= nat.MAX_JOBS)
+
+
 def strata_reads_on_device(fmt, strata=True, demux=False, coords=False,
                            sizes=False, outmap=False, outcov=False, part=None,
                            n_jobs=1, replay=False, own_text=True):
@@ -229,6 +248,7 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
         self._dcover = None         # the `Coverage` of the file on the device text route (`--outcov`)
         # demultiplexing on the device (csrc/wk_demux.hpp)
         self._ddemux = None         # (whitelist or None,) while a file is read that way
+        self._dhdemux = None        # ... likewise for the coord-match (`_run_dhits_demux`)
         self._dx_names = None       # the device's sample table: slot -> name (None: not begun)
         self._dx_key = None         # (epoch, samples) the device holds groups for
         self._dx_full = False       # the table refused a block of this file: the rest on the host
@@ -413,7 +433,7 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
                       want_strings=True, want_samples=False, cover=None,
                       fmt='sam', part=None, words=False, dmaps=None,
                       keep_empty=False, words_dev=False, dcover=False,
-                      ddemux=None, dreads=False):
+                      ddemux=None, dreads=False, dhdemux=None):
         """SAM text -> packed chunks through the native tokenizer.  Yields
         (reads or None, packed, strata ids, name descriptors, sample ids,
         ranges) where packed = (subj, qoff) of subject indices, or for
@@ -430,7 +450,10 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
         there (`_run_ddemux`).  ``dreads`` (`strata_reads_on_device`): plain
         classification with ``want_groups`` -- while the device holds the
         sample's strata map the reads' strata are joined there and the blocks
-        counted as CSR chunks (`_run_dstrata_reads`)."""
+        counted as CSR chunks (`_run_dstrata_reads`).  ``dhdemux``
+        (`demux_hits_on_device`): (whitelist or None,) -- coord-match with
+        ``want_samples``: the samples are told on the device and the blocks'
+        hits staged with a group per read (`_run_dhits_demux`)."""
         from .align import native_sam_blocks
         if self.tok is None:
             # (a tokenizer whose dictionary was filled from this file's first
@@ -441,9 +464,13 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
                 warm = None
             self.tok = warm or nat.Tokenizer(tokenizer_threads(), exclude)
         tok = self.tok
+        dhdemux = dhdemux if (dhdemux is not None and want_samples and
+                              ordinal and cover is None and not want_names
+                              and not want_groups and not exclude) else None
         device_ex = ordinal and cover is None and not want_names and \
             (not want_groups or self._dstrata is not None) and \
-            not want_samples and len(self.jobs) <= nat.MAX_JOBS
+            (not want_samples or dhdemux is not None) and \
+            len(self.jobs) <= nat.MAX_JOBS
         # (the device tokenises SAM, BLAST tabular text and PAF in both
         # flavours, simple maps in the plain one -- they have no other:
         # align.py:258-547, 621-674, 753-981, 984-1213)
@@ -492,7 +519,8 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
                 self._dcover = cover if dcover else None
                 self._ddemux = ddemux
                 self._dreads = dreads
-                if ddemux is not None or dreads:
+                self._dhdemux = dhdemux if device_ex else None
+                if ddemux is not None or dreads or self._dhdemux is not None:
                     # (the reader started before the hierarchy was read is
                     # not taken under `--demux` or with a strata map: the
                     # engine's own reader, as for a file whose turn has come)
@@ -501,7 +529,7 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
                     # (six kernels and a lookup per block: neither the
                     # one-kernel tokenizer nor scan and emission in one wait)
                     self._spec = False
-                if ddemux is not None:
+                if ddemux is not None or self._dhdemux is not None:
                     self._dx_full = False
                     if self._dx_names is None:
                         self.ctx.demux_begin(True)
@@ -529,6 +557,7 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
                     self._dmaps = None
                     self._dcover = None
                     self._ddemux = None
+                    self._dhdemux = None
                     self._dreads = False
                     if getattr(self.ctx, '_h', None):   # (still open)
                         self.ctx.dtok_keep_reads(False)
@@ -758,6 +787,7 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
     ROUTE_OF = {'dtok': '_run_dtok',        # text scanned on the device -> packed records (routes/device_text.py)
                 'dcover': '_run_dcover',    # ... for the "ex" parsers under `--outcov`: ranges to the coverage pile, then the same
                 'dhits': '_run_dhits',      # text scanned on the device -> coord-match hits
+                'dhits_demux': '_run_dhits_demux',  # ... demultiplexed: the hits with their reads' samples as groups
                 'ddemux': '_run_ddemux',    # text scanned on the device -> demultiplexed CSR chunk, counted by the general evaluator
                 'dreads': '_run_dstrata_reads',     # ... -> CSR chunk with the reads' strata joined on the device, counted likewise
                 'words': '_run_words'}      # packed records of the host tokenizer (routes/words.py)

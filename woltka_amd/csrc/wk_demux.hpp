@@ -26,6 +26,10 @@
 //              read's first record its offset, its sample's group and the sample's "met"
 //              byte (demux_place_reads_kernel).
 //
+//   coord-match  behind a scan of the "ex" flavour the lookup asks only for readings that have a hit; the hits are
+//              staged with a group per read (demux_place_hits_kernel) and matched like any staged chunk; the "met"
+//              bytes are stored behind the match, for the reads that matched a gene (demux_met_hits_kernel).
+//
 // Limits: at most kDemuxMaxSamples samples (the table is half full then); a block that
 // would bring more is left to the host tokenizer (kDemuxFull).
 #pragma once
@@ -146,6 +150,9 @@ __device__ __forceinline__ void demux_claim(const DemuxArgs& d, uint32_t idx, un
 
 // a thread per line; the lines that lead a run look their run's samples up (behind dtok_runs and, where they run,
 // dtok_submap / dtok_excl_*: a run whose reads are all dropped brings no sample)
+// kEx: behind a scan of the "ex" flavour (coord-match) a reading brings its sample only when it has a hit -- a mapped
+// line of aligned length > 0 (ordinal.py:231): ordinal_mapper never yields a read whose hits are all of length 0
+template <bool kEx>
 __global__ void __launch_bounds__(kDtokThreads) demux_lookup_kernel(DtokArgs a, DemuxArgs d) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.n_lines) return;
@@ -155,7 +162,7 @@ __global__ void __launch_bounds__(kDtokThreads) demux_lookup_kernel(DtokArgs a, 
     bool need[2] = {false, false};
     uint32_t j = i;
     do {
-        if (a.lsubj[j] >= 0) need[(a.lmeta[j] >> 28) ? 1 : 0] = true;
+        if (a.lsubj[j] >= 0 && (!kEx || a.llen[j] > 0u)) need[(a.lmeta[j] >> 28) ? 1 : 0] = true;
         ++j;
     } while (j < a.n_lines && !a.is_start[j]);
     const DemuxName n0 = demux_sample(a, i, 0u), n1 = demux_sample(a, i, 1u);
@@ -265,6 +272,68 @@ __global__ void __launch_bounds__(kDtokThreads) demux_place_reads_kernel(DtokArg
             d.c_qoff[r] = (int32_t)at;
             d.c_group[r] = g;
         }
+    }
+}
+
+// The "ex" flavour's block as the staged hits of the coord-match with a group per read (the counterpart of
+// dtok_place_kernel): behind dtok_hits<true> and the line scan, a thread per hit.  The hits go where dtok_place_kernel
+// puts them; a read's first hit also looks the read's sample up: its group (-1: outside the whitelist) and its id in
+// the table, for demux_met_hits_kernel -- whether the sample is met is known only once the read has matched a gene.
+__global__ void __launch_bounds__(kDtokThreads) demux_place_hits_kernel(DtokArgs a, DemuxArgs d, int32_t* __restrict__ rsamp) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n_lines || !(a.is_first[i] & 1u)) return;
+    const uint32_t m = a.lmeta[i] >> 28;
+    // the run: back to its start, forward to its end
+    uint32_t s = i, before = 0, mine = 0, groups_before = 0;
+    bool seen[3] = {false, false, false};
+    while (!a.is_start[s]) {
+        --s;
+        if (a.is_first[s] & 1u) {
+            const uint32_t q = a.lmeta[s] >> 28;
+            before += q < m ? 1u : 0u;
+            mine += q == m ? 1u : 0u;
+            if (q < 3u) seen[q] = true;
+        }
+    }
+    for (uint32_t j = i + 1u; j < a.n_lines && !a.is_start[j]; ++j)
+        if (a.is_first[j] & 1u) {
+            const uint32_t q = a.lmeta[j] >> 28;
+            before += q < m ? 1u : 0u;
+            if (q < 3u) seen[q] = true;
+        }
+    const unsigned long long base = a.line_scan[s];  // hits / reads before the run
+    const uint32_t at = (uint32_t)base + before + mine;
+    if (at < d.cap) {
+        const int32_t sid = a.lsubj[i];
+        a.o_genome[at] = (uint32_t)sid < a.n_gmap ? a.gmap[sid] : -1;
+        a.o_beg[at] = a.lbeg[i];
+        a.o_end[at] = a.lend[i];
+        a.o_len[at] = a.llen[i];
+    }
+    if (a.is_first[i] & 2u) {  // the read's first hit: its offset, its sample
+        for (uint32_t q = 0; q < m && q < 3u; ++q) groups_before += seen[q] ? 1u : 0u;
+        const uint32_t r = (uint32_t)(base >> 32) + groups_before;
+        const DemuxName nm = demux_sample(a, i, m ? 1u : 0u);
+        const int32_t id = demux_find(d, a.text + nm.off, nm.len, demux_hash(d, a.text + nm.off, nm.len));
+        if (id < 0) atomicOr(&d.state[0], kDemuxMissing);
+        if (r < d.cap) {
+            a.o_hoff[r] = (int32_t)at;
+            d.c_group[r] = id < 0 ? -1 : d.group[id];
+            rsamp[r] = id;
+        }
+    }
+}
+
+// behind wk_ordinal_match, a thread per read: a read that matched a gene and whose sample the whitelist keeps makes
+// its sample one the reference has met (a plain store: every writer stores 1)
+__global__ void __launch_bounds__(kDtokThreads) demux_met_hits_kernel(const int32_t* __restrict__ qoff, const int32_t* __restrict__ group,
+                                                                      const int32_t* __restrict__ rsamp, int64_t n_reads, uint32_t n_samples,
+                                                                      unsigned char* __restrict__ met) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_reads) return;
+    if (qoff[r + 1] > qoff[r] && group[r] >= 0) {
+        const int32_t id = rsamp[r];
+        if ((uint32_t)id < n_samples) met[id] = 1;
     }
 }
 

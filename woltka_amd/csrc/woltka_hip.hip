@@ -447,6 +447,8 @@ struct wk_ctx {
     bool dx_runs = false;                 // ... and its run starts are told, its subject map and exclusion set applied
     int dx_status = 1;                    // ... and what it found
     bool dx_chunk = false;                // the staged chunk is wk_dtok_stage_reads' or wk_dtok_stage_reads_strata's
+    bool dx_hits = false;                 // the staged hits are wk_dtok_stage_hits_demux': the match marks the samples met
+    DevBuf dx_rsamp;                      // ... and the sample id of every read of theirs (-1: not in the table)
     int32_t dx_groups_n = 0;              // samples that have a group (wk_demux_register)
     uint64_t dx_hash_mask = 0;            // (tests) option "demux_hash_mask"
     int64_t dx_max_opt = 0;               // (tests) option "demux_max_samples"
@@ -1160,7 +1162,7 @@ void wk_destroy(wk_ctx* c) {
     for (DevBuf* b : {&c->d_tiles, &c->d_tile_off, &c->d_lines, &c->d_lsubj, &c->d_lmeta, &c->d_start, &c->d_first, &c->d_unknown, &c->d_lbeg, &c->d_lend, &c->d_llen, &c->d_lscan, &c->d_gmap,
                       &c->d_state, &c->d_dict, &c->d_dict2, &c->d_names16, &c->d_arena, &c->d_submap, &c->cv_key[0], &c->cv_key[1], &c->cv_end[0], &c->cv_end[1],
                       &c->cv_reach, &c->cv_hist, &c->cv_tiles, &c->cv_tile_off, &c->cv_state, &c->cv_stage[0], &c->cv_stage[1], &c->cv_stage[2],
-                      &c->dx_tab, &c->dx_name_off, &c->dx_arena, &c->dx_group, &c->dx_met, &c->dx_pend, &c->dx_pend_list, &c->dx_state, &c->dx_lsamp, &c->dx_out})
+                      &c->dx_tab, &c->dx_name_off, &c->dx_arena, &c->dx_group, &c->dx_met, &c->dx_pend, &c->dx_pend_list, &c->dx_state, &c->dx_lsamp, &c->dx_out, &c->dx_rsamp})
         b->release();
     for (wk_ctx::ResidentText& r : c->resident) {
         (void)hipFree(r.dev);
@@ -1756,6 +1758,7 @@ int wk_chunk_stage(wk_ctx* c, const int32_t* subj, const int32_t* qoff, int64_t 
     c->n_reads = n_reads;
     c->n_records = n_rec;
     c->has_group = group != nullptr && !uniform;
+    c->dx_hits = false;
     c->group_base = uniform ? group[0] : 0;
     c->subj_is_set = (subj_flags & WK_SUBJ_IS_SET) != 0;
     c->subj_indexed = (subj_flags & WK_SUBJ_INDEXED) != 0;
@@ -4953,6 +4956,8 @@ static hipError_t grow_keep(wk_ctx* c, DevBuf& b, size_t need, size_t keep) {
     return hipSuccess;
 }
 
+static int reads_runs_once(wk_ctx* c, const DtokArgs& a, dim3 grid);
+
 static int dtok_stage_impl(wk_ctx* c, const int32_t* genome_of_subject, int32_t n_subjects, double th, bool append, int64_t* n_reads,
                            int64_t* n_hits, int* status) {
     if (!c || !n_reads || !n_hits || !status || n_subjects < 0 || (n_subjects > 0 && !genome_of_subject)) return WK_E_ARG;
@@ -4994,7 +4999,7 @@ static int dtok_stage_impl(wk_ctx* c, const int32_t* genome_of_subject, int32_t 
         HIP_TRY(c, hipMemsetAsync(scalar_u64(c, 3), 0, 8, c->stream));
         const dim3 grid(n_tiles);
         KernelTimer* kt = ktimer_begin(c, "dtok_emit");
-        hipLaunchKernelGGL(dtok_runs_kernel, grid, dim3(kDtokThreads), 0, c->stream, a);
+        if ((rc = reads_runs_once(c, a, grid))) return rc;
         hipLaunchKernelGGL(dtok_hits_kernel<true>, grid, dim3(kDtokThreads), 0, c->stream, a, c->d_tiles.as<unsigned long long>());
         hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_tiles.as<unsigned long long>(),
                            c->d_tile_off.as<unsigned long long>(), (int64_t)n_tiles, scalar_u64(c, 3));
@@ -5027,6 +5032,7 @@ static int dtok_stage_impl(wk_ctx* c, const int32_t* genome_of_subject, int32_t 
     c->chunk_valid = false;
     c->acc_open = append;
     c->dx_chunk = false;
+    c->dx_hits = false;
     *n_reads = reads;
     *n_hits = hits;
     *status = 0;
@@ -5066,6 +5072,7 @@ int wk_demux_begin(wk_ctx* c, int on) {
     c->dx_on = on != 0;
     c->dx_looked = false;
     c->dx_chunk = false;
+    c->dx_hits = false;
     c->dx_groups_n = 0;
     c->dx_name_off_host.clear();
     c->dx_arena_host.clear();
@@ -5091,7 +5098,7 @@ int wk_demux_begin(wk_ctx* c, int on) {
 static int reads_runs_once(wk_ctx* c, const DtokArgs& a, dim3 grid) {
     if (c->dx_runs) return WK_OK;
     hipLaunchKernelGGL(dtok_runs_kernel, grid, dim3(kDtokThreads), 0, c->stream, a);
-    if (a.submap && !c->dt_mapped) {
+    if (a.submap && !c->dt_mapped && !c->dt_extra) {  // (the "ex" flavour's ids go through `genome_of_subject`)
         hipLaunchKernelGGL(dtok_submap_kernel, grid, dim3(kDtokThreads), 0, c->stream, a);
         if (c->dt_has_excl) {
             HIP_TRY(c, hipMemsetAsync(c->d_first.p, 0, c->dt_lines, c->stream));
@@ -5130,7 +5137,10 @@ static int demux_lookup(wk_ctx* c) {
         const int rc = reads_runs_once(c, a, grid);
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(demux_lookup_kernel, grid, dim3(kDtokThreads), 0, c->stream, a, d);
+    if (c->dt_extra)
+        hipLaunchKernelGGL(demux_lookup_kernel<true>, grid, dim3(kDtokThreads), 0, c->stream, a, d);
+    else
+        hipLaunchKernelGGL(demux_lookup_kernel<false>, grid, dim3(kDtokThreads), 0, c->stream, a, d);
     hipLaunchKernelGGL(demux_verify_kernel, grid, dim3(kDtokThreads), 0, c->stream, a, d);
     ktimer_end(c, kt);  // (the launches alone: the waits below are the host's)
     HIP_TRY(c, hipGetLastError());
@@ -5211,7 +5221,8 @@ int wk_demux_pending(wk_ctx* c, int64_t* off, int32_t* len, int32_t cap, int32_t
     *status = 1;
     if (!c->dx_on) return fail(c, WK_E_STATE, "wk_demux_begin has not been called");
     if (!c->dx_looked) {
-        if (!c->dt_ready || c->dt_extra) return fail(c, WK_E_STATE, "no block scanned for the plain flavour (wk_dtok_scan)");
+        // (either flavour: the "ex" flavour's block goes on to wk_dtok_stage_hits_demux)
+        if (!c->dt_ready) return fail(c, WK_E_STATE, "no block scanned (wk_dtok_scan)");
         const int rc = demux_lookup(c);
         if (rc) return rc;
     }
@@ -5302,6 +5313,7 @@ static int stage_reads_chunk(wk_ctx* c, bool strata, int64_t* n_reads, int64_t* 
     c->dx_looked = false;
     c->chunk_valid = false;
     c->dx_chunk = false;
+    c->dx_hits = false;
     const uint32_t lines = c->dt_lines;
     const size_t n_samples = strata ? 0 : c->dx_name_off_host.size();
     if (n_samples) HIP_TRY(c, hipMemsetAsync(c->dx_met.p, 0, n_samples, c->stream));
@@ -5380,13 +5392,119 @@ static int stage_reads_chunk(wk_ctx* c, bool strata, int64_t* n_reads, int64_t* 
 int wk_demux_fetch(wk_ctx* c, int32_t* group, int64_t group_cap, unsigned char* met, int32_t met_cap) {
     if (!c || group_cap < 0 || met_cap < 0) return WK_E_ARG;
     if (!c->dx_on) return fail(c, WK_E_STATE, "wk_demux_begin has not been called");
-    if (!c->dx_chunk || !c->chunk_valid) return fail(c, WK_E_STATE, "no chunk staged by wk_dtok_stage_reads");
+    if (!(c->dx_chunk || c->dx_hits) || !c->chunk_valid)
+        return fail(c, WK_E_STATE, "no chunk staged by wk_dtok_stage_reads, none matched behind wk_dtok_stage_hits_demux");
     const size_t n_samples = c->dx_name_off_host.size();
     if ((group && group_cap < c->n_reads) || (met && (size_t)met_cap < n_samples)) return fail(c, WK_E_CAPACITY, "fetch buffers too small");
     DeviceGuard guard(c->device);
     if (group && c->n_reads) HIP_TRY(c, hipMemcpyAsync(group, c->c_group.p, (size_t)c->n_reads * 4, hipMemcpyDeviceToHost, c->stream));
     if (met && n_samples) HIP_TRY(c, hipMemcpyAsync(met, c->dx_met.p, n_samples, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return WK_OK;
+}
+
+// The block scanned last for the "ex" flavour as the staged hits of the coord-match, a read's group its sample's
+// (demux_place_hits_kernel).  *status stays 1 for a block the host tokenizer takes.
+int wk_dtok_stage_hits_demux(wk_ctx* c, const int32_t* genome_of_subject, int32_t n_subjects, double th, int64_t* n_reads, int64_t* n_hits,
+                             int* status) {
+    if (!c || !n_reads || !n_hits || !status || n_subjects < 0 || (n_subjects > 0 && !genome_of_subject)) return WK_E_ARG;
+    *status = 1;
+    *n_reads = *n_hits = 0;
+    if (!c->dx_on) return fail(c, WK_E_STATE, "wk_demux_begin has not been called");
+    if (!c->dt_ready || !c->dt_extra) return fail(c, WK_E_STATE, "no block scanned for the \"ex\" flavour (wk_dtok_scan)");
+    if (!(th > 0.0)) return fail(c, WK_E_ARG, "overlap threshold must be positive");
+    if (c->dx_groups_n != (int32_t)c->dx_name_off_host.size()) return fail(c, WK_E_STATE, "samples without a group (wk_demux_register)");
+    if (c->acc_open) return fail(c, WK_E_STATE, "staged hits not counted yet (wk_ordinal_count)");
+    DeviceGuard guard(c->device);
+    KtScope kt_scope(c);
+    if (!c->dx_looked) {
+        const int rc = demux_lookup(c);
+        if (rc) return rc;
+    }
+    if (c->dx_status != 0) {
+        c->dt_ready = false;
+        return WK_OK;
+    }
+    if (!c->dx_pend_off.empty()) return fail(c, WK_E_STATE, "the block brings samples the table does not hold (wk_demux_pending, wk_demux_register)");
+    c->dt_ready = false;
+    c->dx_looked = false;
+    c->chunk_valid = false;
+    c->dx_chunk = false;
+    c->dx_hits = false;
+    c->ord_valid = false;
+    const uint32_t lines = c->dt_lines;
+    if ((int64_t)lines >= (1ll << 31) - 64) return fail(c, WK_E_RANGE, "more than 2^31 hits staged");
+    const size_t n_samples = c->dx_name_off_host.size();
+    if (n_samples) HIP_TRY(c, hipMemsetAsync(c->dx_met.p, 0, n_samples, c->stream));
+    int rc;
+    if ((rc = upload(c, c->d_gmap, genome_of_subject, (size_t)std::max(n_subjects, 1) * 4))) return rc;
+    const size_t cap_h = (size_t)lines + 1;
+    HIP_TRY(c, c->o_genome.reserve(cap_h * 4));
+    HIP_TRY(c, c->o_beg.reserve(cap_h * 4));
+    HIP_TRY(c, c->o_end.reserve(cap_h * 4));
+    HIP_TRY(c, c->o_len.reserve(cap_h * 4));
+    HIP_TRY(c, c->o_hoff.reserve(((size_t)lines + 2) * 4));
+    HIP_TRY(c, c->c_group.reserve(((size_t)lines + 1) * 4));
+    HIP_TRY(c, c->dx_rsamp.reserve(((size_t)lines + 1) * 4));
+    unsigned long long totals = 0;
+    uint32_t st[4] = {0, 0, 0, 0};
+    DtokState ds{};
+    if (lines > 0) {
+        DtokArgs a = dtok_args(c);
+        a.gmap = c->d_gmap.as<int32_t>();
+        a.n_gmap = (uint32_t)n_subjects;
+        a.o_genome = c->o_genome.as<int32_t>();
+        a.o_beg = c->o_beg.as<int32_t>();
+        a.o_end = c->o_end.as<int32_t>();
+        a.o_len = c->o_len.as<uint32_t>();
+        a.o_hoff = c->o_hoff.as<int32_t>();
+        a.o_hit_base = 0u;
+        const uint32_t n_tiles = (lines + kDtokThreads - 1) / kDtokThreads;
+        HIP_TRY(c, c->d_tiles.reserve((size_t)n_tiles * 8));
+        HIP_TRY(c, c->d_tile_off.reserve((size_t)n_tiles * 8));
+        HIP_TRY(c, hipMemsetAsync(scalar_u64(c, 3), 0, 8, c->stream));
+        HIP_TRY(c, hipMemsetAsync(c->dx_state.p, 0, 16, c->stream));
+        DemuxArgs d = demux_args(c);
+        d.c_group = c->c_group.as<int32_t>();
+        d.cap = lines;
+        const dim3 grid(n_tiles);
+        KernelTimer* kt = ktimer_begin(c, "demux_stage_hits");
+        if ((rc = reads_runs_once(c, a, grid))) return rc;  // (the lookup of the samples has told the runs)
+        hipLaunchKernelGGL(dtok_hits_kernel<true>, grid, dim3(kDtokThreads), 0, c->stream, a, c->d_tiles.as<unsigned long long>());
+        hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_tiles.as<unsigned long long>(),
+                           c->d_tile_off.as<unsigned long long>(), (int64_t)n_tiles, scalar_u64(c, 3));
+        hipLaunchKernelGGL(dtok_scan_lines_kernel, grid, dim3(kDtokThreads), 0, c->stream, a, c->d_tile_off.as<unsigned long long>());
+        hipLaunchKernelGGL(demux_place_hits_kernel, grid, dim3(kDtokThreads), 0, c->stream, a, d, c->dx_rsamp.as<int32_t>());
+        ktimer_end(c, kt);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, small_back(c, 0, c->d_state.p, sizeof ds));
+        HIP_TRY(c, small_back(c, 1, scalar_u64(c, 3), 8));
+        HIP_TRY(c, small_back(c, 2, c->dx_state.p, 16));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        small_back_get(c, 0, &ds, sizeof ds);
+        small_back_get(c, 1, &totals, 8);
+        small_back_get(c, 2, st, 16);
+    }
+    // (a full table, a name that is not registered, a flag of the scan's: the host tokenizer's block)
+    if (ds.flags || st[0]) return WK_OK;
+    const int64_t hits = (int64_t)(totals & 0xFFFFFFFFull), reads = (int64_t)(totals >> 32);
+    if (hits > (int64_t)lines || reads > hits) return fail(c, WK_E_STATE, "the block's hits do not add up");
+    // (the offsets' last entry; the stream orders it in front of whatever reads them)
+    hipLaunchKernelGGL(store_u32_kernel, dim3(1), dim3(1), 0, c->stream, c->o_hoff.as<uint32_t>() + reads, (uint32_t)hits);
+    HIP_TRY(c, hipGetLastError());
+    c->n_hits = hits;
+    c->o_reads = reads;
+    c->th = th;
+    c->has_group = true;
+    c->group_base = 0;
+    c->rk_valid[0] = c->rk_valid[1] = false;
+    c->ord_valid = true;
+    c->sb_valid = false;
+    c->acc_open = false;
+    c->dx_hits = true;
+    *n_reads = reads;
+    *n_hits = hits;
+    *status = 0;
     return WK_OK;
 }
 
@@ -5465,6 +5583,7 @@ int wk_ordinal_stage(wk_ctx* c, const int32_t* genome, const int32_t* beg, const
     c->o_reads = n_reads;
     c->th = th;
     c->has_group = group != nullptr;
+    c->dx_hits = false;
     c->group_base = 0;
     c->rk_valid[0] = c->rk_valid[1] = false;
     c->ord_valid = true;
@@ -5615,7 +5734,14 @@ int wk_ordinal_match(wk_ctx* c) {
         if ((rc = launch_match_hits(c, true))) return rc;
         ktimer_end(c, kt);
     }
-    return materialise_gene_lists(c);
+    if ((rc = materialise_gene_lists(c))) return rc;
+    if (c->dx_hits && c->o_reads > 0) {  // (the samples whose reads matched a gene: in front of whatever classifies or fetches the chunk)
+        hipLaunchKernelGGL(demux_met_hits_kernel, dim3((unsigned)((c->o_reads + kDtokThreads - 1) / kDtokThreads)), dim3(kDtokThreads), 0,
+                           c->stream, c->o_qoff.as<int32_t>(), c->c_group.as<int32_t>(), c->dx_rsamp.as<int32_t>(), c->o_reads,
+                           (uint32_t)c->dx_name_off_host.size(), c->dx_met.as<unsigned char>());
+        HIP_TRY(c, hipGetLastError());
+    }
+    return WK_OK;
 }
 
 int wk_ordinal_hit_offsets(wk_ctx* c, int32_t* poff, int64_t cap) {

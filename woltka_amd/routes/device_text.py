@@ -1,7 +1,8 @@
 """Alignment text tokenised on the device (csrc/wk_dtok.hpp): blocks read
 into pinned memory, scanned, and appended as packed records (`_run_dtok`) or
 staged as coord-match hits (`_run_dhits`) or, demultiplexed there
-(csrc/wk_demux.hpp), as CSR chunks with a group per read (`_run_ddemux`); read
+(csrc/wk_demux.hpp), as CSR chunks with a group per read (`_run_ddemux`) or as
+coord-match hits with a group per read (`_run_dhits_demux`); read
 maps formatted there (csrc/wk_readmap.hpp) and the strata map joined there
 (csrc/wk_strata.hpp) -- with the hits of the coord-match, or with the reads of
 plain classification (csrc/wk_strata_reads.hpp, `_run_dstrata_reads`).
@@ -1175,11 +1176,21 @@ class DeviceTextRoute:
                             np.fromiter((gidx(x, -1) for x in fresh),
                                         np.int32, len(fresh))])
                     if status == 0:
-                        if n_lines:
+                        if n_lines and self._dhdemux is not None:
+                            yield None, ('dhits_demux', (
+                                text, fill, first, final, hdr_in, hdr,
+                                n_lines)), None, None, None, None
+                        elif n_lines:
                             yield None, ('dhits', (text, fill, first, final,
                                                    hdr_in, hdr)), \
                                 None, None, None, None
                         tok.set_header_state(hdr)
+                    elif self._dhdemux is not None:
+                        # (the scan left the block to the host tokenizer:
+                        # `_run_dhits_demux` hands it over, no lines given)
+                        yield None, ('dhits_demux', (
+                            text, fill, first, final, hdr_in, hdr, None)), \
+                            None, None, None, None
                     else:
                         yield from self._host_block(
                             text, fill, first, final, hdr_in, True,
@@ -1422,7 +1433,7 @@ class DeviceTextRoute:
         names, for the read maps; ``cover``: the "ex" parsers' records with
         their ranges (coverage subject id, beg, end) as the last item;
         ``samples``: with the reads' sample ids, numbered like
-        `_tok_samples`, as the fifth item; ``groups``: with the reads' strata,
+        `_tok_samples`, as the fifth item (``ordinal`` too); ``groups``: with the reads' strata,
         joined on the host and numbered like the device's labels, as the
         third item)."""
         ROUTES['host_block'] += 1
@@ -1436,7 +1447,9 @@ class DeviceTextRoute:
             tok.set_subject_map(self._tok_genome)
             res = tok.parse(memoryview(buf).cast('B')[:fill], first=first,
                             final=final, extra=True, fmt=self._dfmt,
-                            want_groups=groups)
+                            want_groups=groups, want_samples=samples)
+            if samples:
+                self._tok_samples.extend(tok.new_samples())
             fresh = tok.new_subjects()
             if fresh:       # (names met for the first time in this block:
                 gidx = self.genes.genome_index.get      # map them, once more)
@@ -1448,12 +1461,14 @@ class DeviceTextRoute:
                 tok.set_header_state(hdr_in)
                 res = tok.parse(memoryview(buf).cast('B')[:fill], first=first,
                                 final=final, extra=True, fmt=self._dfmt,
-                                want_groups=groups)
+                                want_groups=groups, want_samples=samples)
+                if samples:
+                    self._tok_samples.extend(tok.new_samples())
             if res['off'].size > 1:
                 yield None, (res['subj'], res['beg'], res['end'], res['len'],
                              res['off']), \
                     (self._host_strata_ids(res['group']) if groups else None), \
-                    None, None, None
+                    None, (res['sample'] if samples else None), None
             return
         if groups:      # (the join of this block on the host)
             self._host_strata_table()
@@ -1726,6 +1741,69 @@ class DeviceTextRoute:
                                 packed_is_set=not self._dtrimsub)
         self.tok.set_header_state(hdr)
         return n
+
+    def _run_dhits_demux(self, data, packed, sample):
+        """A block the device has scanned for the coord-match under `--demux`
+        (`_run_ddemux` and `_run_dhits` joined): the samples of its reads that
+        have a hit are registered (`wk_demux_pending` / `_register`), its hits
+        are staged with their reads' samples as groups
+        (`wk_dtok_stage_hits_demux`), matched and counted
+        (`wk_ordinal_count`); a sample gets its profiles once one of its
+        reads has matched a gene (`wk_demux_fetch`), as `workflow.demultiplex`
+        behind `ordinal_mapper` has it.  A block the kernels refuse -- more
+        samples than the table holds, a name that is not registered -- goes
+        through the host tokenizer with the samples told there."""
+        buf, fill, first, final, hdr_in, hdr, n_lines = packed[1]
+        allow, = self._dhdemux
+        # (no lines given: the scan left the block to the host tokenizer)
+        status, fresh = (1, []) if self._dx_full or n_lines is None \
+            else self.ctx.demux_pending()
+        if status == 0:
+            names = self._dx_names
+            if fresh:
+                names.extend(x.decode() for x in fresh)
+            # room for the groups and the count keys the block can add (before
+            # its groups are taken: a fold numbers them anew)
+            if len(self.groups) + len(names) + 1 >= MAX_GROUPS // 2:
+                self.collect(data)
+            self._ensure_table(data, 4 * (fill // 24 + 1),
+                               min(n_lines, len(names) + 1))
+            key = (self._epoch, len(names))
+            if fresh or self._dx_key != key:
+                self.ctx.demux_register(fresh,
+                                        self._device_sample_groups(allow))
+                self._dx_key = key
+            # (queries that matched a gene are asked once per file,
+            # `take_deferred`, as in `_run_dhits`)
+            if self._deferred_from is None:
+                self._deferred_from = self.ctx.stats()['n_reads']
+            status, n_reads, _ = self.ctx.dtok_stage_hits_demux(
+                self._tok_genome, self._th)
+        elif status & 1 and n_lines is not None:
+            self._dx_full = True    # (the rest of the file: the host's)
+        if status == 0:
+            ROUTES['dhits_demux'] += 1
+            self._n_reads += n_reads
+            if n_reads:
+                self.ctx.ordinal_count(self.jobs)
+                if self.sizes:
+                    self._collect_log()
+                met, _ = self.ctx.demux_fetch(len(self._dx_names))
+                for i in np.flatnonzero(met).tolist():
+                    s = self._dx_names[i]
+                    for rank in self.ranks:
+                        data[rank].setdefault(s, {})
+            return 0
+        if self._deferred_from is None:
+            self._deferred_from = self.ctx.stats()['n_reads']
+        for _, arrays, _, _, ids, _ in self._host_block(
+                buf, fill, first, final, hdr_in, True, samples=True):
+            # (its queries are among those `take_deferred` reports)
+            self.run_chunk(data, None, None, None, None, None, None, None,
+                           None, True, packed=arrays, sample_ids=ids,
+                           allow=allow)
+        self.tok.set_header_state(hdr)
+        return 0
 
     def _run_dstrata_reads(self, data, packed, sample):
         """A block the device has scanned for plain classification while it

@@ -24,7 +24,8 @@ import click
 import numpy as np
 
 from .align import NATIVE_FORMATS, infer_align_format, plain_mapper
-from .classify import (Engine, cover_on_device, demux_on_device,
+from .classify import (Engine, cover_on_device, demux_hits_on_device,
+                       demux_on_device,
                        exact_to_numbers, strata_reads_on_device)
 from .file import (FilesAhead, id2file_from_dir, id2file_from_map, openzip, path2stem,
                    read_ids, read_map_1st, read_map_uniq, readzip, readzip_bytes,
@@ -528,6 +529,13 @@ def classify(
                             ddemux=(allow,) if demux_on_device(
                                 native_demux, fmt_, coords=bool(ordinal),
                                 sizes=bool(sizes), n_jobs=len(engine.jobs),
+                                replay=engine._replay is not None) else None,
+                            # ... and for the coord-match (`_run_dhits_demux`)
+                            dhdemux=(allow,) if ordinal and
+                            demux_hits_on_device(
+                                native_demux, fmt_, sizes=bool(sizes),
+                                exclude=bool(exclude),
+                                n_jobs=len(engine.jobs),
                                 replay=engine._replay is not None) else None,
                             dreads=dreads)
                         if ordinal and rank2dir is not None:
