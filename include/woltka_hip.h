@@ -630,6 +630,43 @@ int wk_dtok_stage_reads_strata(wk_ctx* ctx, int64_t* n_reads,
                                int64_t* n_records, int* status);
 int wk_chunk_groups(wk_ctx* ctx, int32_t* group, int64_t cap);
 
+/* Read maps of whole-read assignments on the device
+ * (csrc/wk_readmap_reads.hpp): `--outmap` for job sets in which every job
+ * gives a read one feature or none -- `--rank free`, a rank under --uniq /
+ * --above / --major, none under --uniq (classify.py:32-141) -- so that a line
+ * is `query[/mate] <tab> feature` (file.write_readmap, file.py:469-500), or
+ * `query[/mate] <tab> Unassigned` under --unassigned (workflow.py:1038-1039).
+ *   wk_dtok_stage_reads_plain  behind a wk_dtok_scan of the plain flavour
+ *                      (status 0), demultiplexing off: the block as the staged
+ *                      classify chunk, as wk_dtok_stage_reads_strata leaves it,
+ *                      but with no group per read: wk_set_uniform_group names
+ *                      the one group of all of them.  The reads stand in the
+ *                      order the parser yields them (align.py:327-332) and
+ *                      their leader lines are kept for wk_dtok_readmap_reads.
+ *                      *status != 0: nothing is staged, the host tokenizer
+ *                      takes the block (a read of more than WK_MAX_K subjects,
+ *                      a name without a subject).
+ *   wk_classify_staged_keep  wk_classify_staged with the codes (feature id or
+ *                      WK_ASSIGN_*, job-major) left on the device instead of
+ *                      copied out; the counts are the same.
+ *   wk_readmap_reads_tables  the shown-text table: features [first, first + n)
+ *                      print shown[shown_off[k], shown_off[k + 1]) (the id, or
+ *                      its name under --name-as-id).  first = 0 sets the table,
+ *                      first = its size extends it (subjects interned since);
+ *                      it covers the hierarchy's nodes and the names outside
+ *                      it alike.
+ *   wk_dtok_readmap_reads  the text of the staged chunk at job j, from the
+ *                      codes wk_classify_staged_keep left for it: *n_bytes =
+ *                      its size (0: no lines); wk_dtok_readmap_fetch copies it
+ *                      out.  WK_E_STATE if a code is a list, "no candidates"
+ *                      or a feature outside the table: no text then. */
+int wk_dtok_stage_reads_plain(wk_ctx* ctx, int64_t* n_reads,
+                              int64_t* n_records, int* status);
+int wk_classify_staged_keep(wk_ctx* ctx, const wk_job* jobs, int32_t n_jobs);
+int wk_readmap_reads_tables(wk_ctx* ctx, int32_t first, int32_t n,
+                            const uint32_t* shown_off, const char* shown);
+int wk_dtok_readmap_reads(wk_ctx* ctx, int32_t job, int64_t* n_bytes);
+
 /* Convenience: stage + classify in one call from host buffers. */
 int wk_classify_chunk(wk_ctx* ctx, const wk_job* jobs, int32_t n_jobs,
                       const int32_t* subj, const int32_t* qoff,

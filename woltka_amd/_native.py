@@ -66,6 +66,8 @@ SYMBOLS = (
     'wk_demux_begin', 'wk_demux_pending', 'wk_demux_register',
     'wk_dtok_stage_reads', 'wk_demux_fetch', 'wk_dtok_stage_hits_demux',
     'wk_dtok_stage_reads_strata', 'wk_chunk_groups',
+    'wk_dtok_stage_reads_plain', 'wk_classify_staged_keep',
+    'wk_readmap_reads_tables', 'wk_dtok_readmap_reads',
     'wk_tok_subjects',
     'wk_tok_new_subjects', 'wk_tok_fetch_groups', 'wk_tok_strata_clear',
     'wk_tok_strata_load', 'wk_tok_strata_labels', 'wk_tok_strata_select',
@@ -276,6 +278,12 @@ def load_library():
         'wk_dtok_stage_reads_strata': (C.c_int, [p, i64p, i64p,
                                                  C.POINTER(C.c_int)]),
         'wk_chunk_groups': (C.c_int, [p, i32p, C.c_int64]),
+        'wk_dtok_stage_reads_plain': (C.c_int, [p, i64p, i64p,
+                                                C.POINTER(C.c_int)]),
+        'wk_classify_staged_keep': (C.c_int, [p, C.POINTER(Job), C.c_int32]),
+        'wk_readmap_reads_tables': (C.c_int, [p, C.c_int32, C.c_int32, u32p,
+                                              C.c_void_p]),
+        'wk_dtok_readmap_reads': (C.c_int, [p, C.c_int32, i64p]),
         'wk_tok_subjects': (C.c_int, [p, i32p, i32p, i64p]),
         'wk_tok_new_subjects': (C.c_int, [p, C.c_char_p, i32p]),
         'wk_tok_fetch_groups': (C.c_int, [p, i32p]),
@@ -1124,6 +1132,55 @@ class Context:
             self._h, _ptr(group, C.c_int32) if group.size else None,
             group.size))
         return group
+
+    # -- read maps of whole-read assignments (csrc/wk_readmap_reads.hpp) --
+    def dtok_stage_reads_plain(self):
+        """The scanned block (plain flavour, demultiplexing off) as the staged
+        classify chunk with no group per read (``set_uniform_group`` names
+        the one of all of them), its reads' leader lines kept for
+        ``dtok_readmap_reads``.  Returns (status, reads, records); status !=
+        0: the host tokenizer takes the block."""
+        a, b, st = C.c_int64(0), C.c_int64(0), C.c_int(1)
+        self._check(self._lib.wk_dtok_stage_reads_plain(
+            self._h, C.byref(a), C.byref(b), C.byref(st)))
+        if st.value == 0:
+            self._n_reads = a.value
+        return st.value, a.value, b.value
+
+    def classify_staged_keep(self, jobs):
+        """``classify_staged`` with the assignment codes left on the device
+        (for ``dtok_readmap_reads``); nothing comes back."""
+        self._check(self._lib.wk_classify_staged_keep(
+            self._h, self._jobs(jobs), len(jobs)))
+
+    def readmap_reads_tables(self, first, blob, off):
+        """The shown-text table of ``dtok_readmap_reads``: features ``first``
+        .. ``first + off.size - 1`` print ``blob[off[k]:off[k + 1]]`` (uint8 /
+        uint32 arrays).  ``first`` = 0 sets the table, ``first`` = its size
+        extends it."""
+        off = _arr(off, np.uint32)
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        if off.size < 1 or int(off[-1]) != blob.size:
+            raise ValueError('offsets must run from 0 to the size of the text')
+        self._check(self._lib.wk_readmap_reads_tables(
+            self._h, int(first), off.size - 1, _ptr(off, C.c_uint32),
+            C.c_void_p(blob.ctypes.data if blob.size else 0)))
+
+    def dtok_readmap_reads(self, job, out=None):
+        """Read-map text of the chunk ``dtok_stage_reads_plain`` staged last
+        at job ``job``, from the codes ``classify_staged_keep`` left: a uint8
+        array (``out``: a buffer to fetch it into when it is large enough) and
+        whether it lies in ``out``."""
+        n = C.c_int64(0)
+        self._check(self._lib.wk_dtok_readmap_reads(self._h, int(job),
+                                                    C.byref(n)))
+        inside = out is not None and out.size >= n.value
+        if not inside:
+            out = np.empty(n.value, dtype=np.uint8)
+        if n.value:
+            self._check(self._lib.wk_dtok_readmap_fetch(
+                self._h, C.c_void_p(out.ctypes.data), out.size))
+        return out[:n.value], inside
 
     def ordinal_hit_offsets(self, n_hits):
         """Offsets of every hit's genes in the staged gene lists

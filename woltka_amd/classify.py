@@ -270,6 +270,9 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
         # strata map joined on the device (csrc/wk_strata.hpp)
         self._dstrata = None        # {'fp', 'labels', 'slots', 'key'} while the device holds the sample's map
         self._dreads = False        # plain classification of the file is joined with it there (csrc/wk_strata_reads.hpp)
+        # read maps of whole-read assignments formatted on the device (csrc/wk_readmap_reads.hpp)
+        self._dreadmaps = None      # (rank2dir, outzip, namedic) while a file is read that way
+        self._shown_sent = None     # (namedic, features) the device's shown-text table covers
         self._sbuf = [None, None]   # pinned buffers the map text is inflated into
         self._sbuf_next = 0
 
@@ -433,7 +436,8 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
                       want_strings=True, want_samples=False, cover=None,
                       fmt='sam', part=None, words=False, dmaps=None,
                       keep_empty=False, words_dev=False, dcover=False,
-                      ddemux=None, dreads=False, dhdemux=None):
+                      ddemux=None, dreads=False, dhdemux=None,
+                      dreadmaps=None):
         """SAM text -> packed chunks through the native tokenizer.  Yields
         (reads or None, packed, strata ids, name descriptors, sample ids,
         ranges) where packed = (subj, qoff) of subject indices, or for
@@ -453,7 +457,11 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
         counted as CSR chunks (`_run_dstrata_reads`).  ``dhdemux``
         (`demux_hits_on_device`): (whitelist or None,) -- coord-match with
         ``want_samples``: the samples are told on the device and the blocks'
-        hits staged with a group per read (`_run_dhits_demux`)."""
+        hits staged with a group per read (`_run_dhits_demux`).
+        ``dreadmaps`` (`read_maps_on_device`): (rank2dir, outzip, namedic) --
+        plain classification with read maps of a set in which no job returns
+        a list: the blocks are counted as CSR chunks, the codes stay on the
+        device and the maps are formatted there (`_run_dreads_maps`)."""
         from .align import native_sam_blocks
         if self.tok is None:
             # (a tokenizer whose dictionary was filled from this file's first
@@ -487,12 +495,18 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
                       and not ordinal and cover is None and not want_names
                       and not want_samples and part is None
                       and len(self.jobs) <= nat.MAX_JOBS)
+        dreadmaps = dreadmaps if (
+            dreadmaps is not None and not (words or words_dev or dmaps) and
+            not ordinal and cover is None and not want_groups and
+            not want_samples and part is None and
+            len(self.jobs) <= nat.MAX_JOBS) else None
         if (words or words_dev or device_ex or dmaps or dcover or
-                ddemux is not None or dreads) and (
+                ddemux is not None or dreads or dreadmaps is not None) and (
                 fmt in ('sam', 'b6o', 'paf') or (fmt == 'map' and
                                                  not ordinal)) and \
                 (not exclude or ((words or words_dev or ddemux is not None
-                                  or dreads) and not dmaps)) and \
+                                  or dreads or dreadmaps is not None)
+                                 and not dmaps)) and \
                 not os.environ.get('WOLTKA_NO_DTOK'):
             from .align import _parallel_reader, part_range
             from .file import GunzipStream
@@ -519,8 +533,10 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
                 self._dcover = cover if dcover else None
                 self._ddemux = ddemux
                 self._dreads = dreads
+                self._dreadmaps = dreadmaps
                 self._dhdemux = dhdemux if device_ex else None
-                if ddemux is not None or dreads or self._dhdemux is not None:
+                if ddemux is not None or dreads or dreadmaps is not None or \
+                        self._dhdemux is not None:
                     # (the reader started before the hierarchy was read is
                     # not taken under `--demux` or with a strata map: the
                     # engine's own reader, as for a file whose turn has come)
@@ -559,6 +575,7 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
                     self._ddemux = None
                     self._dhdemux = None
                     self._dreads = False
+                    self._dreadmaps = None
                     if getattr(self.ctx, '_h', None):   # (still open)
                         self.ctx.dtok_keep_reads(False)
                 return
@@ -790,6 +807,7 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
                 'dhits_demux': '_run_dhits_demux',  # ... demultiplexed: the hits with their reads' samples as groups
                 'ddemux': '_run_ddemux',    # text scanned on the device -> demultiplexed CSR chunk, counted by the general evaluator
                 'dreads': '_run_dstrata_reads',     # ... -> CSR chunk with the reads' strata joined on the device, counted likewise
+                'dreads_maps': '_run_dreads_maps',  # ... -> CSR chunk of one group, counted likewise, read maps formatted from the codes on the device
                 'words': '_run_words'}      # packed records of the host tokenizer (routes/words.py)
 
     def _run_general(self, data, reads, subque, sample_of, strata_of, trimsub,

@@ -88,12 +88,10 @@ __device__ __forceinline__ int readmap_taxa(const DtokArgs& a, const ReadmapArgs
     return n;
 }
 
-// a thread per line; leaders (bit 1 of is_first, dtok_scan_lines_kernel) work
-__global__ void __launch_bounds__(kDtokThreads) readmap_len_kernel(DtokArgs a, ReadmapArgs m) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.n_lines || !(a.is_first[i] & 2u)) return;
+// The index of the read whose leader is line i (bit 1 of is_first, dtok_scan_lines_kernel): reads before the
+// run + mates of the run that come first (align.py:327-332).
+__device__ __forceinline__ uint32_t readmap_read_index(const DtokArgs& a, uint32_t i) {
     const uint32_t mate = a.lmeta[i] >> 28;
-    // the read's index: reads before the run + mates of the run that come first (align.py:327-332)
     uint32_t s = i;
     bool seen[3] = {false, false, false};
     while (!a.is_start[s]) {
@@ -110,7 +108,15 @@ __global__ void __launch_bounds__(kDtokThreads) readmap_len_kernel(DtokArgs a, R
         }
     uint32_t before = 0;
     for (uint32_t q = 0; q < mate && q < 3u; ++q) before += seen[q] ? 1u : 0u;
-    const uint32_t r = (uint32_t)(a.line_scan[s] >> 32) + before;
+    return (uint32_t)(a.line_scan[s] >> 32) + before;
+}
+
+// a thread per line; leaders work
+__global__ void __launch_bounds__(kDtokThreads) readmap_len_kernel(DtokArgs a, ReadmapArgs m) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n_lines || !(a.is_first[i] & 2u)) return;
+    const uint32_t mate = a.lmeta[i] >> 28;
+    const uint32_t r = readmap_read_index(a, i);
     if (r >= m.n_reads) return;
     int32_t slot[WK_WEIGHT_MAX_K];
     uint32_t count[WK_WEIGHT_MAX_K];

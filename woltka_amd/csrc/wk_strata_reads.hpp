@@ -27,6 +27,8 @@ struct StrataChunk {
 // place = records before its run + records of lower mates in the run + its position in its read; a read's index
 // likewise from its first record (the places demux_place_reads_kernel computes).  The read's first record alone looks
 // its id up: QNAME (+ "/1" | "/2" for a mate) as the per-line arrays of the plain flavour have it.
+// kJoin = false: no map, no group per read (the caller names one group for the chunk): the places alone.
+template <bool kJoin>
 __global__ void __launch_bounds__(kDtokThreads) strata_place_reads_kernel(DtokArgs a, StrataArgs strata, StrataChunk ch) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.n_lines || !(a.is_first[i] & 1u)) return;
@@ -59,7 +61,8 @@ __global__ void __launch_bounds__(kDtokThreads) strata_place_reads_kernel(DtokAr
     if (a.is_first[i] & 2u) {  // the read's first record
         for (uint32_t q = 0; q < m && q < 3u; ++q) groups_before += seen[q] ? 1u : 0u;
         const uint32_t r = (uint32_t)(base >> 32) + groups_before;
-        const int32_t g = strata_lookup(strata, a.text + a.line_start[i], a.lmeta[i] & 0x0FFFFFFFu, m);
+        int32_t g = 0;
+        if constexpr (kJoin) g = strata_lookup(strata, a.text + a.line_start[i], a.lmeta[i] & 0x0FFFFFFFu, m);
         if (r < ch.cap) {
             ch.c_qoff[r] = (int32_t)at;
             ch.c_group[r] = g;

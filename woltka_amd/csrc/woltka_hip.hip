@@ -30,6 +30,7 @@
 #include "wk_ordinal.hpp"
 #include "wk_stripe.hpp"
 #include "wk_readmap.hpp"
+#include "wk_readmap_reads.hpp"
 #include "wk_tok_internal.h"
 #include "wk_weigh.hpp"
 #include "wk_weigh_wide.hpp"
@@ -455,7 +456,16 @@ struct wk_ctx {
     bool dt_keep_reads = false;   // wk_dtok_keep_reads: wk_dtok_emit places the records in read order and keeps the block
     bool dt_emitted = false;      // the block scanned last was emitted with its reads kept
     uint32_t dt_emit_reads = 0;
-    int64_t rm_bytes = 0;         // text of the last wk_dtok_readmap
+    int64_t rm_bytes = 0;         // text of the last wk_dtok_readmap / wk_dtok_readmap_reads
+    // read maps of whole-read assignments (wk_readmap_reads.hpp): the shown-text table over the feature ids, the
+    // kernels' flags; what the codes wk_classify_staged_keep left in assign_out belong to
+    DevBuf rr_off, rr_text, rr_flags;
+    int32_t rr_n = 0;             // features the table covers
+    uint32_t rr_text_n = 0;       // bytes of their text
+    bool rr_chunk = false;        // the staged chunk is wk_dtok_stage_reads_plain's: its reads' leader lines are in rm_line
+    int64_t rr_serial = -1;       // stage_serial of the chunk whose codes assign_out holds ...
+    int32_t rr_jobs = 0;          // ... and the jobs they were written for
+    uint32_t rr_unassigned = 0;   // ... under --unassigned
     int range_parts_opt = 0;   // partitions of the dense gene log (0: as few as the merge's LDS array allows; measurement)
     int use_streams = 1;   // (0: the records of all slices in one stream, round 3's team kernel; measurement)
     int use_subject_bins = 1;
@@ -1162,7 +1172,8 @@ void wk_destroy(wk_ctx* c) {
     for (DevBuf* b : {&c->d_tiles, &c->d_tile_off, &c->d_lines, &c->d_lsubj, &c->d_lmeta, &c->d_start, &c->d_first, &c->d_unknown, &c->d_lbeg, &c->d_lend, &c->d_llen, &c->d_lscan, &c->d_gmap,
                       &c->d_state, &c->d_dict, &c->d_dict2, &c->d_names16, &c->d_arena, &c->d_submap, &c->cv_key[0], &c->cv_key[1], &c->cv_end[0], &c->cv_end[1],
                       &c->cv_reach, &c->cv_hist, &c->cv_tiles, &c->cv_tile_off, &c->cv_state, &c->cv_stage[0], &c->cv_stage[1], &c->cv_stage[2],
-                      &c->dx_tab, &c->dx_name_off, &c->dx_arena, &c->dx_group, &c->dx_met, &c->dx_pend, &c->dx_pend_list, &c->dx_state, &c->dx_lsamp, &c->dx_out, &c->dx_rsamp})
+                      &c->dx_tab, &c->dx_name_off, &c->dx_arena, &c->dx_group, &c->dx_met, &c->dx_pend, &c->dx_pend_list, &c->dx_state, &c->dx_lsamp, &c->dx_out, &c->dx_rsamp,
+                      &c->rr_off, &c->rr_text, &c->rr_flags})
         b->release();
     for (wk_ctx::ResidentText& r : c->resident) {
         (void)hipFree(r.dev);
@@ -1764,11 +1775,32 @@ int wk_chunk_stage(wk_ctx* c, const int32_t* subj, const int32_t* qoff, int64_t 
     c->subj_indexed = (subj_flags & WK_SUBJ_INDEXED) != 0;
     c->chunk_valid = true;
     c->dx_chunk = false;
+    c->rr_chunk = false;
     return WK_OK;
 }
 
+static int classify_staged_impl(wk_ctx* c, const wk_job* jobs, int32_t n_jobs, int32_t* out_assign, bool keep);
+
 int wk_classify_staged(wk_ctx* c, const wk_job* jobs, int32_t n_jobs, int32_t* out_assign) {
+    return classify_staged_impl(c, jobs, n_jobs, out_assign, false);
+}
+
+// The same with the codes left where classify_kernel writes them (assign_out, job-major) and nothing copied to
+// the host: wk_dtok_readmap_reads formats the read maps from them.
+int wk_classify_staged_keep(wk_ctx* c, const wk_job* jobs, int32_t n_jobs) {
+    const int rc = classify_staged_impl(c, jobs, n_jobs, nullptr, true);
+    if (rc) return rc;
+    c->rr_serial = c->stage_serial;
+    c->rr_jobs = n_jobs;
+    c->rr_unassigned = (jobs[0].flags & WK_F_UNASSIGNED) ? 1u : 0u;
+    return WK_OK;
+}
+
+// `keep`: the codes are written as for `out_assign` and stay on the device.
+static int classify_staged_impl(wk_ctx* c, const wk_job* jobs, int32_t n_jobs, int32_t* out_assign, bool keep) {
     if (!c) return WK_E_ARG;
+    c->rr_serial = -1;  // (whatever assign_out held is overwritten or stale from here on)
+    const bool want_codes = out_assign != nullptr || keep;
     if (!jobs || n_jobs < 1 || n_jobs > WK_MAX_JOBS) return fail(c, WK_E_ARG, "n_jobs must be in [1,%d]", WK_MAX_JOBS);
     if (!c->chunk_valid) return fail(c, WK_E_STATE, "no chunk staged");
     if (!c->slots) return fail(c, WK_E_STATE, "count table not reserved (wk_counts_reserve)");
@@ -1831,7 +1863,7 @@ int wk_classify_staged(wk_ctx* c, const wk_job* jobs, int32_t n_jobs, int32_t* o
         }
         a.n_cols = n_cols;
     }
-    if (out_assign) {
+    if (want_codes) {
         HIP_TRY(c, c->assign_out.reserve((size_t)n_jobs * (size_t)(c->n_reads ? c->n_reads : 1) * sizeof(int32_t)));
         a.out_assign = c->assign_out.as<int32_t>();
     }
@@ -1868,7 +1900,7 @@ int wk_classify_staged(wk_ctx* c, const wk_job* jobs, int32_t n_jobs, int32_t* o
                                (feature_chunk ? a.n_cols >= 0 : (a.row_w == 4 && c->n_subjects < (1 << 28)));
             // ... and with a small subject table the first pass only histograms
             // subject indices; the assigners run once per subject afterwards
-            const bool subject_ok = split && !feature_chunk && c->use_subject_bins && !out_assign && !c->has_group && !sized;
+            const bool subject_ok = split && !feature_chunk && c->use_subject_bins && !want_codes && !c->has_group && !sized;
             const bool by_subject = subject_ok && c->n_subjects <= 28672;
             // a larger table: the first 24,576 subject indices (first appearance
             // order: the abundant ones) in bins, the others per read
@@ -1876,7 +1908,7 @@ int wk_classify_staged(wk_ctx* c, const wk_job* jobs, int32_t n_jobs, int32_t* o
             constexpr int kHotBins = 24576;
             // weighted subject histogram (wk_weigh.hpp): plain assigners only, every
             // read a set of subject indices, one group, no per-read output
-            bool weigh = !ext && c->use_weigh && c->subj_indexed && c->subj_is_set && !c->has_group && !out_assign && !sized &&
+            bool weigh = !ext && c->use_weigh && c->subj_indexed && c->subj_is_set && !c->has_group && !want_codes && !sized &&
                          c->n_reads < (1ll << 30) && c->n_records < (1ll << 30) && c->n_subjects > 0;
             for (int j = 0; j < n_jobs && weigh; ++j) {
                 if (jobs[j].mode == WK_MODE_NONE)
@@ -5032,6 +5064,7 @@ static int dtok_stage_impl(wk_ctx* c, const int32_t* genome_of_subject, int32_t 
     c->chunk_valid = false;
     c->acc_open = append;
     c->dx_chunk = false;
+    c->rr_chunk = false;
     c->dx_hits = false;
     *n_reads = reads;
     *n_hits = hits;
@@ -5072,6 +5105,7 @@ int wk_demux_begin(wk_ctx* c, int on) {
     c->dx_on = on != 0;
     c->dx_looked = false;
     c->dx_chunk = false;
+    c->rr_chunk = false;
     c->dx_hits = false;
     c->dx_groups_n = 0;
     c->dx_name_off_host.clear();
@@ -5278,7 +5312,8 @@ int wk_demux_register(wk_ctx* c, const char* blob, const int64_t* off, int32_t n
     return WK_OK;
 }
 
-static int stage_reads_chunk(wk_ctx* c, bool strata, int64_t* n_reads, int64_t* n_records, int* status);
+enum StageReads { kStageDemux = 0, kStageStrata = 1, kStagePlain = 2 };
+static int stage_reads_chunk(wk_ctx* c, StageReads how, int64_t* n_reads, int64_t* n_records, int* status);
 
 int wk_dtok_stage_reads(wk_ctx* c, int64_t* n_reads, int64_t* n_records, int* status) {
     if (!c || !n_reads || !n_records || !status) return WK_E_ARG;
@@ -5302,17 +5337,22 @@ int wk_dtok_stage_reads(wk_ctx* c, int64_t* n_reads, int64_t* n_records, int* st
         }
         if (!c->dx_pend_off.empty()) return fail(c, WK_E_STATE, "the block brings samples the table does not hold (wk_demux_pending, wk_demux_register)");
     }
-    return stage_reads_chunk(c, false, n_reads, n_records, status);
+    return stage_reads_chunk(c, kStageDemux, n_reads, n_records, status);
 }
 
 // The block scanned last for the plain flavour as the staged CSR chunk with a group per read: the group of the read's
 // sample (wk_demux.hpp; the samples have been looked up) or, `strata`, of its stratum in the map that is loaded
-// (wk_strata_reads.hpp).  *status stays 1 for a block the kernels leave to the host tokenizer.
-static int stage_reads_chunk(wk_ctx* c, bool strata, int64_t* n_reads, int64_t* n_records, int* status) {
+// (wk_strata_reads.hpp) -- or, kStagePlain, with no group per read at all: the caller names the one group of all of
+// them (wk_set_uniform_group), and the reads' leader lines are kept for wk_dtok_readmap_reads (wk_readmap_reads.hpp).
+// *status stays 1 for a block the kernels leave to the host tokenizer.
+static int stage_reads_chunk(wk_ctx* c, StageReads how, int64_t* n_reads, int64_t* n_records, int* status) {
+    const bool strata = how != kStageDemux;  // (run starts told here; no samples to look up)
+    const bool plain = how == kStagePlain;
     c->dt_ready = false;
     c->dx_looked = false;
     c->chunk_valid = false;
     c->dx_chunk = false;
+    c->rr_chunk = false;
     c->dx_hits = false;
     const uint32_t lines = c->dt_lines;
     const size_t n_samples = strata ? 0 : c->dx_name_off_host.size();
@@ -5333,7 +5373,7 @@ static int stage_reads_chunk(wk_ctx* c, bool strata, int64_t* n_reads, int64_t* 
         HIP_TRY(c, hipMemsetAsync(scalar_u64(c, 3), 0, 8, c->stream));
         if (!strata) HIP_TRY(c, hipMemsetAsync(c->dx_state.p, 0, 16, c->stream));
         const dim3 grid(n_tiles);
-        KernelTimer* kt = ktimer_begin(c, strata ? "strata_stage" : "demux_stage");
+        KernelTimer* kt = ktimer_begin(c, plain ? "reads_stage" : strata ? "strata_stage" : "demux_stage");
         if (strata) {  // (under `--demux` the lookup of the samples has told the runs)
             const int rc = reads_runs_once(c, a, grid);
             if (rc) return rc;
@@ -5345,7 +5385,10 @@ static int stage_reads_chunk(wk_ctx* c, bool strata, int64_t* n_reads, int64_t* 
         hipLaunchKernelGGL(dtok_scan_lines_kernel, grid, dim3(kDtokThreads), 0, c->stream, a, c->d_tile_off.as<unsigned long long>());
         if (strata) {
             const StrataChunk ch{c->c_subj.as<int32_t>(), c->c_qoff.as<int32_t>(), c->c_group.as<int32_t>(), lines};
-            hipLaunchKernelGGL(strata_place_reads_kernel, grid, dim3(kDtokThreads), 0, c->stream, a, strata_args(c), ch);
+            if (plain)
+                hipLaunchKernelGGL(strata_place_reads_kernel<false>, grid, dim3(kDtokThreads), 0, c->stream, a, StrataArgs{}, ch);
+            else
+                hipLaunchKernelGGL(strata_place_reads_kernel<true>, grid, dim3(kDtokThreads), 0, c->stream, a, strata_args(c), ch);
         } else {
             DemuxArgs d = demux_args(c);
             d.c_subj = c->c_subj.as<int32_t>();
@@ -5375,14 +5418,25 @@ static int stage_reads_chunk(wk_ctx* c, bool strata, int64_t* n_reads, int64_t* 
     c->stage_serial += 1;
     c->cur_subj = c->c_subj.as<int32_t>();
     c->cur_qoff = c->c_qoff.as<int32_t>();
+    if (plain && reads > 0) {
+        // the leader line of every read, in the chunk's read order (a read no leader names keeps "no line")
+        HIP_TRY(c, c->rm_line.reserve((size_t)reads * 4));
+        HIP_TRY(c, hipMemsetAsync(c->rm_line.p, 0xFF, (size_t)reads * 4, c->stream));
+        DtokArgs a = dtok_args(c);
+        a.line_scan = c->d_lscan.as<unsigned long long>();
+        hipLaunchKernelGGL(readmap_leaders_kernel, dim3((lines + kDtokThreads - 1) / kDtokThreads), dim3(kDtokThreads), 0, c->stream, a,
+                           c->rm_line.as<uint32_t>(), (uint32_t)reads);
+        HIP_TRY(c, hipGetLastError());
+    }
     c->n_reads = reads;
     c->n_records = records;
-    c->has_group = true;
+    c->has_group = !plain;
     c->group_base = 0;
     c->subj_is_set = true;
     c->subj_indexed = true;
     c->chunk_valid = true;
-    c->dx_chunk = true;
+    c->dx_chunk = !plain;
+    c->rr_chunk = plain;
     *n_reads = reads;
     *n_records = records;
     *status = 0;
@@ -5430,6 +5484,7 @@ int wk_dtok_stage_hits_demux(wk_ctx* c, const int32_t* genome_of_subject, int32_
     c->dx_looked = false;
     c->chunk_valid = false;
     c->dx_chunk = false;
+    c->rr_chunk = false;
     c->dx_hits = false;
     c->ord_valid = false;
     const uint32_t lines = c->dt_lines;
@@ -5520,7 +5575,7 @@ int wk_dtok_stage_reads_strata(wk_ctx* c, int64_t* n_reads, int64_t* n_records, 
     if (c->acc_open) return fail(c, WK_E_STATE, "staged hits not counted yet (wk_ordinal_count)");
     DeviceGuard guard(c->device);
     KtScope kt_scope(c);
-    return stage_reads_chunk(c, true, n_reads, n_records, status);
+    return stage_reads_chunk(c, kStageStrata, n_reads, n_records, status);
 }
 
 int wk_chunk_groups(wk_ctx* c, int32_t* group, int64_t cap) {
@@ -5530,6 +5585,106 @@ int wk_chunk_groups(wk_ctx* c, int32_t* group, int64_t cap) {
     DeviceGuard guard(c->device);
     if (c->n_reads) HIP_TRY(c, hipMemcpyAsync(group, c->c_group.p, (size_t)c->n_reads * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return WK_OK;
+}
+
+// ---- read maps of whole-read assignments on the device (wk_readmap_reads.hpp) ------------------------------------
+
+int wk_dtok_stage_reads_plain(wk_ctx* c, int64_t* n_reads, int64_t* n_records, int* status) {
+    if (!c || !n_reads || !n_records || !status) return WK_E_ARG;
+    *status = 1;
+    *n_reads = *n_records = 0;
+    if (c->dx_on) return fail(c, WK_E_STATE, "the reads' groups are their samples' (wk_demux_begin): wk_dtok_stage_reads");
+    if (!c->dt_ready || c->dt_extra) return fail(c, WK_E_STATE, "no block scanned for the plain flavour (wk_dtok_scan)");
+    if (c->acc_open) return fail(c, WK_E_STATE, "staged hits not counted yet (wk_ordinal_count)");
+    DeviceGuard guard(c->device);
+    KtScope kt_scope(c);
+    return stage_reads_chunk(c, kStagePlain, n_reads, n_records, status);
+}
+
+int wk_readmap_reads_tables(wk_ctx* c, int32_t first, int32_t n, const uint32_t* shown_off, const char* shown) {
+    if (!c) return WK_E_ARG;
+    if (first < 0 || n < 0 || (n > 0 && !shown_off)) return fail(c, WK_E_ARG, "bad shown-text table");
+    if (first != 0 && first != c->rr_n) return fail(c, WK_E_ARG, "the shown-text table holds %d features: set it from 0 or extend it from there", c->rr_n);
+    if (n > 0 && shown_off[0] != 0) return fail(c, WK_E_ARG, "shown_off must start at 0");
+    for (int32_t k = 0; k < n; ++k)
+        if (shown_off[k + 1] < shown_off[k]) return fail(c, WK_E_ARG, "shown_off must not decrease");
+    const uint32_t n_text = n > 0 ? shown_off[n] : 0u;
+    if (n_text > 0 && !shown) return fail(c, WK_E_ARG, "bad shown-text table");
+    const uint32_t base = first ? c->rr_text_n : 0u;
+    if ((uint64_t)base + n_text >= (1ull << 32) || (int64_t)first + n >= (1ll << 31)) return fail(c, WK_E_RANGE, "shown-text table beyond 2^32 bytes");
+    DeviceGuard guard(c->device);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // (a kernel may be reading the table that is there)
+    HIP_TRY(c, grow_keep(c, c->rr_off, ((size_t)first + n + 1) * 4, first ? ((size_t)first + 1) * 4 : 0));
+    HIP_TRY(c, grow_keep(c, c->rr_text, (size_t)base + n_text + 64, base));
+    std::vector<uint32_t> off((size_t)n + 1);
+    for (int32_t k = 0; k <= n; ++k) off[k] = base + (n > 0 ? shown_off[k] : 0u);
+    HIP_TRY(c, hipMemcpyAsync(c->rr_off.as<uint32_t>() + first, off.data(), off.size() * 4, hipMemcpyHostToDevice, c->stream));
+    if (n_text) HIP_TRY(c, hipMemcpyAsync(c->rr_text.as<unsigned char>() + base, shown, n_text, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // (the caller's buffers are only valid during the call)
+    c->rr_n = first + n;
+    c->rr_text_n = base + n_text;
+    return WK_OK;
+}
+
+int wk_dtok_readmap_reads(wk_ctx* c, int32_t job, int64_t* n_bytes) {
+    if (!c || !n_bytes) return WK_E_ARG;
+    *n_bytes = 0;
+    c->rm_bytes = 0;
+    if (!c->rr_chunk || !c->chunk_valid) return fail(c, WK_E_STATE, "no chunk staged by wk_dtok_stage_reads_plain");
+    if (c->rr_serial != c->stage_serial) return fail(c, WK_E_STATE, "the staged chunk's codes are not on the device (wk_classify_staged_keep)");
+    if (job < 0 || job >= c->rr_jobs) return fail(c, WK_E_ARG, "job must be in [0, %d)", c->rr_jobs);
+    if (c->n_reads >= (1ll << 32) - 1) return fail(c, WK_E_RANGE, "more than 2^32 reads in one block");
+    const uint32_t n_reads = (uint32_t)c->n_reads;
+    if (n_reads == 0 || c->dt_lines == 0) return WK_OK;
+    DeviceGuard guard(c->device);
+    KtScope kt_scope(c);
+    HIP_TRY(c, c->rm_len.reserve((size_t)n_reads * 8));
+    HIP_TRY(c, c->rr_flags.reserve(16));
+    HIP_TRY(c, c->rr_off.reserve(4));  // (an empty table still has its first offset's place)
+    DtokArgs a = dtok_args(c);
+    ReadmapReadsArgs m{};
+    m.assign = c->assign_out.as<int32_t>() + (size_t)job * n_reads;
+    m.read_line = c->rm_line.as<uint32_t>();
+    m.shown_off = c->rr_off.as<uint32_t>();
+    m.shown = c->rr_text.as<unsigned char>();
+    m.n_shown = (uint32_t)c->rr_n;
+    m.read_len = c->rm_len.as<unsigned long long>();
+    m.flags = c->rr_flags.as<uint32_t>();
+    m.n_reads = n_reads;
+    m.unassigned = c->rr_unassigned;
+    const dim3 rgrid((n_reads + kDtokThreads - 1) / kDtokThreads);
+    HIP_TRY(c, c->d_tiles.reserve((size_t)rgrid.x * 8));
+    HIP_TRY(c, c->d_tile_off.reserve((size_t)rgrid.x * 8));
+    HIP_TRY(c, hipMemsetAsync(c->rr_flags.p, 0, 16, c->stream));
+    HIP_TRY(c, hipMemsetAsync(scalar_u64(c, 3), 0, 8, c->stream));
+    KernelTimer* kt = ktimer_begin(c, "readmap_reads");
+    hipLaunchKernelGGL(readmap_reads_len_kernel, rgrid, dim3(kDtokThreads), 0, c->stream, a, m);
+    hipLaunchKernelGGL(u64_tile_sum_kernel, rgrid, dim3(kDtokThreads), 0, c->stream, m.read_len, n_reads, c->d_tiles.as<unsigned long long>());
+    hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_tiles.as<unsigned long long>(),
+                       c->d_tile_off.as<unsigned long long>(), (int64_t)rgrid.x, scalar_u64(c, 3));
+    hipLaunchKernelGGL(u64_tile_prefix_kernel, rgrid, dim3(kDtokThreads), 0, c->stream, m.read_len, n_reads, c->d_tile_off.as<unsigned long long>());
+    HIP_TRY(c, hipGetLastError());
+    unsigned long long total = 0;
+    uint32_t flags = 0;
+    HIP_TRY(c, hipMemcpyAsync(&total, scalar_u64(c, 3), 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&flags, c->rr_flags.p, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (flags) {
+        ktimer_end(c, kt);
+        return fail(c, WK_E_STATE, "job %d left a code that is no single feature of the shown-text table (%d features)", job, c->rr_n);
+    }
+    if (total >= (1ull << 40)) return fail(c, WK_E_RANGE, "read-map text of one block beyond 2^40 bytes");
+    if (total > 0) {
+        HIP_TRY(c, c->rm_text.reserve((size_t)total + 64));
+        m.out = c->rm_text.as<unsigned char>();
+        m.out_cap = total;
+        hipLaunchKernelGGL(readmap_reads_write_kernel, rgrid, dim3(kDtokThreads), 0, c->stream, a, m);
+        HIP_TRY(c, hipGetLastError());
+    }
+    ktimer_end(c, kt);
+    c->rm_bytes = (int64_t)total;
+    *n_bytes = (int64_t)total;
     return WK_OK;
 }
 
@@ -5707,6 +5862,7 @@ static int materialise_gene_lists(wk_ctx* c) {
     c->subj_indexed = false; // gene lists carry feature ids
     c->chunk_valid = true;
     c->dx_chunk = false;
+    c->rr_chunk = false;
     return WK_OK;
 }
 

@@ -5,7 +5,9 @@ staged as coord-match hits (`_run_dhits`) or, demultiplexed there
 coord-match hits with a group per read (`_run_dhits_demux`); read
 maps formatted there (csrc/wk_readmap.hpp) and the strata map joined there
 (csrc/wk_strata.hpp) -- with the hits of the coord-match, or with the reads of
-plain classification (csrc/wk_strata_reads.hpp, `_run_dstrata_reads`).
+plain classification (csrc/wk_strata_reads.hpp, `_run_dstrata_reads`); read
+maps of whole-read assignments formatted there from the assignment codes
+(csrc/wk_readmap_reads.hpp, `_run_dreads_maps`).
 Blocks the kernels leave alone go through the host tokenizer (`_host_block`)."""
 import os
 import time
@@ -1152,7 +1154,7 @@ class DeviceTextRoute:
                 t0 = time.perf_counter()
                 done = None
                 if self._spec and not ex and self._ddemux is None and \
-                        not self._dreads:
+                        not self._dreads and self._dreadmaps is None:
                     # (the sample's words are open and the block before went
                     # through: scan and emission with one wait)
                     status, n_lines, done = self.ctx.dtok_scan_emit(
@@ -1215,6 +1217,10 @@ class DeviceTextRoute:
                         yield None, ('dreads', (text, fill, first, final,
                                                 hdr_in, hdr, n_lines)), \
                             None, None, None, None
+                    elif n_lines and self._dreadmaps is not None:
+                        yield None, ('dreads_maps', (
+                            text, fill, first, final, hdr_in, hdr, n_lines)), \
+                            None, None, None, None
                     elif n_lines:
                         yield None, ('dcover' if cover else 'dtok', (
                             text, fill, first, final, hdr_in, hdr, done)), \
@@ -1224,7 +1230,8 @@ class DeviceTextRoute:
                     self._spec = False
                     yield from self._host_block(text, fill, first, final,
                                                 hdr_in,
-                                                names=self._dmaps is not None,
+                                                names=self._dmaps is not None
+                                                or self._dreadmaps is not None,
                                                 cover=cover,
                                                 samples=self._ddemux is not None,
                                                 groups=self._dreads)
@@ -1248,7 +1255,8 @@ class DeviceTextRoute:
             # one-kernel tokenizer: no newline count behind a block's copy)
             self.ctx.set_option('dtok_count_ahead', int(bool(
                 ex or self._dmaps is not None or self._dfmt != 'sam' or
-                self._ddemux is not None or self._dreads)))
+                self._ddemux is not None or self._dreads or
+                self._dreadmaps is not None)))
         ahead, whole = taken, None
         if ahead is None:
             whole = open_mapped() if source is None else None
@@ -1323,6 +1331,7 @@ class DeviceTextRoute:
                 slot = item[0]
                 if may_lag and self._spec and self._dmaps is None and \
                         self._ddemux is None and not self._dreads and \
+                        self._dreadmaps is None and \
                         isinstance(slot, tuple) and slot[0] == 'det':
                     t0 = time.perf_counter()
                     begun = self.ctx.dtok_scan_emit_begin(tok, item[1],
@@ -1841,6 +1850,74 @@ class DeviceTextRoute:
         self.tok.set_header_state(hdr)
         return n
 
+    def _sync_shown(self, namedic):
+        """The device's shown-text table (wk_readmap_reads_tables) over the
+        feature index as it is now: the ids, or their names under
+        `--name-as-id` -- set once, extended by the features `_sync_subjects`
+        has interned since."""
+        n = len(self.index)
+        have = self._shown_sent
+        if have is not None and have[0] is namedic and have[1] == n:
+            return
+        first = have[1] if have is not None and have[0] is namedic else 0
+        ids = self.index.names_of(range(first, n))
+        shown = [namedic.get(x, x) for x in ids] if namedic else ids
+        # (one encode for all of them: a line feed is in no id or name)
+        blob = np.frombuffer('\n'.join(shown).encode(), dtype=np.uint8)
+        cut = np.flatnonzero(blob == 10)
+        off = np.empty(n - first + 1, dtype=np.int64)
+        off[0] = 0
+        off[1:-1] = cut - np.arange(cut.size)
+        off[-1] = blob.size - cut.size
+        if cut.size != n - first - 1:
+            raise ValueError('a feature id or name holds a line feed')
+        self.ctx.readmap_reads_tables(first, blob[blob != 10],
+                                      off.astype(np.uint32))
+        self._shown_sent = (namedic, n)
+
+    def _run_dreads_maps(self, data, packed, sample):
+        """A block the device has scanned for plain classification with read
+        maps of a job set in which no job returns a list: the block is staged
+        as a CSR chunk of one group (`wk_dtok_stage_reads_plain`) and counted
+        by the general evaluator with the assignment codes left on the device
+        (`wk_classify_staged_keep`); per rank the map text is formatted there
+        from the codes (`wk_dtok_readmap_reads`) and only the text is fetched,
+        into the ring of `_device_maps`.  A block the kernels refuse -- a read
+        of more subjects than a count key can say -- goes through the host
+        tokenizer and the host formatter, and lands in the same files in
+        order."""
+        buf, fill, first, final, hdr_in, hdr, n_lines = packed[1]
+        rank2dir, outzip, namedic = self._dreadmaps
+        self._sync_subjects(data)
+        if (sample, None) not in self.group_ids and \
+                len(self.groups) + 1 >= MAX_GROUPS // 2:
+            self.collect(data)
+        self._ensure_table(data, n_lines, 1)
+        group = self._group_array(1, sample, None)
+        status, n_reads, _ = self.ctx.dtok_stage_reads_plain()
+        if status == 0:
+            ROUTES['dreads_maps'] += 1
+            if n_reads:
+                for rank in self.ranks:
+                    data[rank].setdefault(sample, {})
+                self._sync_shown(namedic)
+                self.ctx.set_uniform_group(group)
+                self.ctx.classify_staged_keep(self.jobs)
+                self._device_maps(sample, rank2dir, outzip, namedic,
+                                  fetch=self.ctx.dtok_readmap_reads)
+            self._n_reads += n_reads
+            return n_reads
+        n = 0
+        for _, (subj, qoff), _, names, *_ in self._host_block(
+                buf, fill, first, final, hdr_in, names=True):
+            self._sync_subjects(data)
+            n += self.run_chunk(data, None, None, sample, None, None,
+                                rank2dir, outzip, namedic, False,
+                                packed=(subj, qoff), names=names,
+                                packed_is_set=not self._dtrimsub)
+        self.tok.set_header_state(hdr)
+        return n
+
     def _sync_map_tables(self, namedic):
         """The device's read-map tables (wk_readmap_tables) over the subject
         table as it is now; False when some subject has no taxon at a rank
@@ -1872,10 +1949,12 @@ class DeviceTextRoute:
 
     MAP_TEXT_SLOT = 24 << 20    # bytes of a pinned buffer for a block's map text
 
-    def _device_maps(self, sample, rank2dir, outzip, namedic):
+    def _device_maps(self, sample, rank2dir, outzip, namedic, fetch=None):
         """The read maps of the block emitted last: text from the device
-        (wk_dtok_readmap), compressed and appended behind this thread's
-        back."""
+        (wk_dtok_readmap; ``fetch``: of the chunk staged last, from its
+        codes, wk_dtok_readmap_reads), compressed and appended behind this
+        thread's back."""
+        fetch = fetch or self.ctx.dtok_readmap
         if self._mring is None:
             self._mring = StageRing(self.ctx, 6, {
                 'text': (np.uint8, self.MAP_TEXT_SLOT)})
@@ -1894,7 +1973,7 @@ class DeviceTextRoute:
                 self._maps_done()
                 self._writer._drain(True, one=True)
                 bufs = ring.try_current()
-            text, inside = self.ctx.dtok_readmap(j, out=bufs['text'])
+            text, inside = fetch(j, out=bufs['text'])
             done = None
             if inside and text.size:
                 done = partial(ring.release, ring.take())

@@ -111,6 +111,42 @@ class WordsRoute:
                 return False
         return True
 
+    def read_maps_on_device(self, fmt, demux=False, strata=False,
+                            coords=False, outcov=False, part=None,
+                            own_text=True):
+        """Can the read maps of this file be formatted on the device from the
+        assignment codes (csrc/wk_readmap_reads.hpp, `_run_dreads_maps`)?
+        Plain classification with `--outmap` of a whole file (``part``) of
+        SAM, BLAST tabular, PAF or simple-map text that can be read block by
+        block (``own_text``: a plain file or a gzip file this package inflates
+        itself), with or without `--trim-sub` / `--exclude`, when no job of the
+        set can return a list: every job is `--rank free`, a rank under --uniq
+        / --above / --major, or none under --uniq (`whole_reads`, or none with
+        --uniq).  Not under ``demux``, ``strata``, ``coords``, ``outcov`` or
+        `--sizes`, not during the replay pass, not with more than `MAX_JOBS`
+        jobs.  A set that holds a job able to return a list keeps today's
+        routes (plain jobs only: `device_maps_eligible`).
+        ``WOLTKA_NO_DREADMAPS=1`` (like ``WOLTKA_NO_DTOK=1``) keeps the
+        general route."""
+        if os.environ.get('WOLTKA_NO_DREADMAPS') or \
+                os.environ.get('WOLTKA_NO_DTOK'):
+            return False
+        if demux or strata or coords or outcov or self.sizes or \
+                self._replay is not None or part is not None or \
+                not own_text or fmt not in ('sam', 'b6o', 'paf', 'map') or \
+                not 1 <= len(self.jobs) <= nat.MAX_JOBS:
+            return False
+        for job in self.jobs:
+            if job.flags & nat.F_SIZED:
+                return False
+            if job.mode == nat.MODE_NONE:
+                if not job.flags & nat.F_UNIQ:
+                    return False
+            elif not (whole_reads(job) or (job.mode == nat.MODE_RANK and
+                                           job.major > 0)):
+                return False
+        return True
+
     def _run_words(self, data, packed, sample):
         """One chunk of packed records (``('words', array, n_reads, slot)``
         from `native_chunks`): appended to the sample's records on the device,

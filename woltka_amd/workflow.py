@@ -516,6 +516,25 @@ def classify(
                                 stratmap or trimsub or want_strings) and \
                                 engine.device_maps_eligible():
                             dmaps = (rank2dir, outzip, namedic)
+                        # ... and of sets in which no job can return a list
+                        # (`--rank free`, --uniq / --above / --major): from
+                        # the assignment codes, which stay on the device
+                        # (csrc/wk_readmap_reads.hpp)
+                        dreadmaps = None
+                        if rank2dir is not None and dmaps is None and \
+                                not want_strings:
+                            from .file import ZIP_BY_EXT, GunzipStream
+                            from os.path import splitext
+                            if engine.read_maps_on_device(
+                                    fmt_, demux=bool(demux),
+                                    strata=bool(stratmap),
+                                    coords=bool(ordinal),
+                                    outcov=cover is not None, part=part,
+                                    own_text=path != '-' and (
+                                        ZIP_BY_EXT.get(splitext(path)[1])
+                                        is None or
+                                        isinstance(stream, GunzipStream))):
+                                dreadmaps = (rank2dir, outzip, namedic)
                         chunks = engine.native_chunks(
                             stream, head, exclude, NATIVE_BLOCK, ordinal,
                             want_names, trimsub, want_groups=native_strata,
@@ -537,7 +556,7 @@ def classify(
                                 exclude=bool(exclude),
                                 n_jobs=len(engine.jobs),
                                 replay=engine._replay is not None) else None,
-                            dreads=dreads)
+                            dreads=dreads, dreadmaps=dreadmaps)
                         if ordinal and rank2dir is not None:
                             chunks = engine.regroup_hits(chunks, n)
                     else:
