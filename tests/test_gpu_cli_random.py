@@ -51,49 +51,67 @@ def _label(i):
     return f'{i}-' + '-'.join(map(str, bits))
 
 
-def expects_device_text(case, args):
-    """Must this reference case be tokenised on the device?  The stated limits
-    of the device text route (DESIGN: routes), nothing more: plain text files
-    in a directory (a single file is demultiplexed), no
-    `--demux`, no coverage, no `--sizes`; plain
-    classification with job sets the packed words take (plain ranks, or
-    whole-read jobs only) with or without read maps; `--coords` without read
-    maps.  Returns the ROUTES keys of which one must have counted."""
+def route_factors(case):
+    """The case's options as factor levels of tests/cli_routes_cases.py (what
+    its `expected_route` reads): a single-file input is demultiplexed, bzip2
+    and xz are both text the package does not read block by block, and a job
+    set is known by its kinds of jobs -- plain ones (`none`, a rank),
+    whole-read ones (`free`, a rank under --uniq / --above / --major above 50), `none`
+    under --uniq."""
     kw = case['kwargs']
-    files = [f for f in case['files'] if f.startswith('aln/')]
-    if not files or kw['input_fp'] != 'aln':
+    files = [f for f in case['files']
+             if f.startswith('aln/') or f.startswith('mux.')]
+    root, zext = os.path.splitext(files[0])
+    if zext not in ('.gz', '.bz2', '.xz'):
+        root, zext = files[0], ''
+    fmt = {'b6': 'b6o'}.get(root.rsplit('.', 1)[1], root.rsplit('.', 1)[1])
+    if kw['input_fp'] == 'aln' and not kw.get('demux'):
+        layout = 'dir-samples' if kw.get('samples') else 'dir'
+    else:
+        layout = 'mux-list' if kw.get('samples') else 'mux'
+    ranks = (kw.get('ranks') or ('rank' if kw.get('map_rank') else 'none')
+             ).split(',')
+    tree = any(kw.get(k) for k in ('nodes_fps', 'lineage_fps', 'columns_fps',
+                                   'newick_fps', 'map_fps'))
+    kinds = set()
+    for r in ranks:
+        if r == 'none' or not tree:
+            kinds.add('none-uniq' if kw.get('uniq') else 'plain')
+        elif r == 'free' or kw.get('uniq') or kw.get('above') or \
+                (kw.get('major') or 0) > 50:
+            kinds.add('whole')
+        else:
+            assert not kw.get('major')      # (<= 50: no level stands for it)
+            kinds.add('plain')
+    jobs = 'none-uniq' if 'none-uniq' in kinds else \
+        'mixed' if kinds == {'plain', 'whole'} else \
+        'whole' if kinds == {'whole'} else \
+        'three' if len(ranks) > 1 else 'one' if ranks != ['none'] else 'none'
+    return dict(
+        fmt=fmt, input=layout, zip=zext if zext in ('', '.gz') else '.bz2',
+        system='coords' if kw.get('coords_fp') else 'plain', jobs=jobs,
+        outmap=bool(case['want_maps']), outcov=bool(case.get('want_cov')),
+        stratify=bool(kw.get('strata_dir')), sizes=bool(kw.get('sizes')),
+        trimsub=bool(kw.get('trimsub')), exclude=bool(kw.get('exclude')),
+        unassigned=bool(kw.get('unassigned')),
+        name_as_id=bool(kw.get('name_as_id')), blocks='one')
+
+
+def expects_device_text(case, args):
+    """Must this reference case be tokenised on the device?  The table of
+    DESIGN.md section 3 as tests/cli_routes_cases.py holds it
+    (`expected_route`, `expected_also`): the ROUTES keys of which one must
+    have counted and those that must have counted next to it, or None."""
+    import cli_routes_cases
+    if not any(f.startswith('aln/') or f.startswith('mux.')
+               for f in case['files']) or 'error' in case['expect']:
         return None
-    # (gzip files are inflated natively and take the same route; bzip2 / xz
-    # text comes through the ordinary decompressors and the host tokenizer)
-    if any(os.path.splitext(f)[1] in ('.bz2', '.xz') for f in files):
+    factors = route_factors(case)
+    want = cli_routes_cases.expected_route(factors)
+    if want is None:
         return None
-    if any(kw.get(k) for k in ('demux', 'sizes', 'strata_dir', 'samples')):
-        return None
-    # (`--exclude`: the plain flavour's kernels drop the runs that hit a name
-    # of the set -- without read maps, not under --coords)
-    if kw.get('exclude') and (kw.get('coords_fp') or case['want_maps']):
-        return None
-    # (`--trim-sub`: the kernels translate the names they meet into subjects,
-    # wk_dtok_subject_map -- plain classification without read maps)
-    if kw.get('trimsub') and (kw.get('coords_fp') or case['want_maps']):
-        return None
-    if case.get('want_cov') or 'error' in case['expect']:
-        return None
-    if kw.get('coords_fp'):
-        return None if case['want_maps'] else ('dhits', 'dhits_strata')
-    ranks = (kw.get('ranks') or 'none').split(',')
-    whole = [r == 'free' or bool(kw.get('uniq') or kw.get('above') or
-                                 (kw.get('major') or 0) > 50)
-             for r in ranks]
-    if kw.get('uniq') and not all(whole):
-        return None             # (--uniq at --rank none: the general route)
-    if any(whole) and not all(whole):
-        return None             # mixed job sets: the general evaluator
-    if kw.get('major') and not all(whole):
-        return None
-    if case['want_maps'] and any(whole):
-        return None             # device read maps: the plain assigners
-    return ('dtok_maps',) if case['want_maps'] else ('dtok',)
+    return tuple(sorted(want)), tuple(sorted(
+        cli_routes_cases.expected_also(factors)))
 
 
 @pytest.mark.parametrize('i', range(len(CASES)), ids=_label)
@@ -144,8 +162,11 @@ def test_random_cli_case(tmp_path, i):
     took = {k: ROUTES[k] - routes_before.get(k, 0) for k in ROUTES
             if ROUTES[k] != routes_before.get(k, 0)}
     if want is not None and any(x.strip() for f, x in case['files'].items()
-                                if f.startswith('aln/')):
-        assert any(took.get(k) for k in want), (want, took)
+                                if f.startswith('aln/') or
+                                f.startswith('mux.')):
+        assert any(took.get(k) for k in want[0]), (want, took)
+        for k in want[1]:
+            assert took.get(k), (want, took)
     if case['want_maps']:
         maps = {}
         for root, _, fns in os.walk(args['outmap_dir']):
