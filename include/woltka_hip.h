@@ -513,8 +513,10 @@ int wk_dtok_readmap_fetch(wk_ctx* ctx, char* out, int64_t cap);
 
 /* `extra` != 0 — the "ex" flavour (align.parse_sam_file_ex + ordinal_mapper,
  * align.py:350-406, ordinal.py:167-240): wk_dtok_scan also takes POS and CIGAR
- * (start, end, aligned length per line; text beyond [+-]digits and
- * (digits op)+ goes back to the host: status 1), and wk_dtok_stage_hits
+ * (start, end, aligned length per line; text beyond [+-]digits -- at most ten
+ * -- and (digits op)+ goes back to the host: status 1, and so does a line
+ * whose start, end or reference span leaves int32, which the host tokenizer
+ * refuses: never a wrapped value), and wk_dtok_stage_hits
  * leaves the block's hits staged exactly as wk_ordinal_stage would have: hits
  * of zero length dropped, the hits of a read (query, mate) contiguous, reads in
  * the order the parser yields them; genome_of_subject[id] = index into the
@@ -762,7 +764,12 @@ int wk_tok_set_exclude(wk_tok* tok, const char* blob, const int32_t* off,
  * the number of bytes used — feed the rest again, followed by more text.
  * `extra` bit 0: also produce POS-1, reference end and aligned length per
  * record ("ex" flavour; zero-length hits are dropped unless bit 1 is set — the
- * coverage mapper, range.py:21, keeps them).  `want_names`: keep a
+ * coverage mapper, range.py:21, keeps them).  A negative aligned length (a
+ * length field or CIGAR number with a minus sign, which int() takes) is an
+ * error, WK_E_RANGE -- the reference stores lengths as uint32 and numpy refuses
+ * the value, ordinal.py:205-233 --, unless bit 2 is set: the caller does not
+ * read the lengths (the coverage mapper, range.py:70) and the record is kept
+ * with length 0.  Never a value wrapped to 32 bits.  `want_names`: keep a
  * descriptor of every read's QNAME.  Results are held by the tokenizer until
  * the next call; sizes are returned in *n_reads / *n_records. */
 int wk_tok_sam(wk_tok* tok, const char* buf, int64_t len, int first_block,

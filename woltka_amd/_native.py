@@ -1354,6 +1354,8 @@ class Tokenizer:
         msg = self._lib.wk_tok_last_error(self._h).decode()
         if rc == E_RANGE and 'mate bits' in msg:
             raise IndexError(msg)       # align.py:339 indexes a 3-tuple with 3
+        if rc == E_RANGE and 'negative aligned length' in msg:
+            raise OverflowError(msg)    # ordinal.py:233 stores it as uint32
         raise ValueError(msg)
 
     def close(self):

@@ -627,8 +627,12 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
             if not ordinal:
                 tok.set_subject_map(None)
             for buf, res in native_sam_blocks(stream, tok, block_bytes,
-                                              extra=3 if (cover is not None
-                                                          or keep_empty)
+                                              # (7: coverage alone never reads
+                                              # the lengths, range.py:70)
+                                              extra=7 if (cover is not None
+                                                          and not ordinal)
+                                              else 3 if (cover is not None
+                                                         or keep_empty)
                                               else int(ordinal),
                                               want_names=want_names,
                                               head=head,

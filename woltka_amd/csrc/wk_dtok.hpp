@@ -601,7 +601,9 @@ __global__ void __launch_bounds__(kDtokThreads) dtok_parse_kernel(DtokArgs a) {
         }
         ok = ok && !have;  // (digits without an operation: the host's parser has its own opinion)
         const long long beg = pos - 1, end = pos - 1 + (long long)(aligned + extra);
-        ok = ok && beg >= -2147483647ll && end <= 2147483647ll && aligned < (1ull << 32);
+        // (the reference span itself within int32 too, as the host tokenizer asks: POS 0 with 2147483648M ends at
+        // 2147483647 and is a loud error there, not a hit)
+        ok = ok && beg >= -2147483647ll && end <= 2147483647ll && aligned < (1ull << 32) && aligned + extra <= 2147483647ull;
         if (!ok) {
             atomicOr(&a.state->flags, kDtokBadNumber);
             return;

@@ -173,6 +173,8 @@ struct Line {
     int32_t beg, end;
     uint32_t len;
     bool bad_number;  // a field Python's int() would refuse (the reference raises; SAM: the FLAG, once the line is kept)
+    bool wide;        // (b6o / paf rows, with bad_number) numbers, but wider than the 32 bits they are held in
+    bool neg_len;     // (b6o / paf rows) a negative aligned length: len holds 0, the caller raises or drops the length
     // the line itself (without its newline) and the hash of its subject name
     const char* line;
     const char* le;
@@ -380,10 +382,11 @@ inline Line parse_row(int fmt, const char* p, const char* e, bool extra) {
         }
         // (coordinates are held in 32 bits: anything wider is a loud error)
         if (!fits_i32(a) || !fits_i32(b) || !fits_i32((a < b ? a : b) - 1) || n > (long)UINT32_MAX || n < -(long)UINT32_MAX) {
-            L.bad_number = true;
+            L.bad_number = L.wide = true;
             return L;
         }
-        L.len = (uint32_t)n;
+        L.neg_len = n < 0;  // (never a value wrapped into the unsigned length)
+        L.len = n < 0 ? 0u : (uint32_t)n;
         L.beg = (int32_t)((a < b ? a : b) - 1);
         L.end = (int32_t)(a < b ? b : a);
     } else {
@@ -393,10 +396,11 @@ inline Line parse_row(int fmt, const char* p, const char* e, bool extra) {
             !parse_int(fb(11), fe(11), sc))
             return L;  // ValueError is caught there: the row is skipped
         if (!fits_i32(a) || !fits_i32(b) || n > (long)UINT32_MAX || n < -(long)UINT32_MAX) {
-            L.bad_number = true;  // (numbers, but wider than the 32 bits they are held in)
+            L.bad_number = L.wide = true;  // (numbers, but wider than the 32 bits they are held in)
             return L;
         }
-        L.len = (uint32_t)n;
+        L.neg_len = n < 0;
+        L.len = n < 0 ? 0u : (uint32_t)n;
         L.beg = (int32_t)a;
         L.end = (int32_t)b;
     }
@@ -742,6 +746,11 @@ template <bool kExtra>
 void tokenize_range(const wk_tok* T, int fmt, const char* base, const char* b, const char* e, int extra_bits, bool want_names,
                     bool want_groups, bool want_samples, Local& out) {
     const bool keep_empty = (extra_bits & 2) != 0;
+    // A negative aligned length (BLAST x[3], PAF x[10], a CIGAR like "-5M": int() takes the sign).  The reference
+    // stores lengths in a uint32 array (ordinal.py:205, 233), where numpy refuses the value: OverflowError.  Its
+    // coverage mapper never looks at the length (range.py:70).  So: a loud error, unless the caller says it does not
+    // read the lengths (bit 2) -- then the record is kept with length 0.  Never the value wrapped to 32 bits.
+    const bool lens_unread = (extra_bits & 4) != 0;
     const bool filt = T->exclude.size() > 0;
     const bool track_pool = kExtra && filt && fmt == WK_FMT_SAM;
     static const char* const kSuffix[3] = {"", "/1", "/2"};
@@ -852,7 +861,7 @@ void tokenize_range(const wk_tok* T, int fmt, const char* base, const char* b, c
                 // like any other short line, align.py:313; the other formats skip it)
                 if (le == line && fmt != WK_FMT_SAM) continue;
                 if (fmt != WK_FMT_SAM && !L.bad_number) continue;  // not a row of this format
-                out.error = 2;
+                out.error = fmt != WK_FMT_SAM && L.wide ? 3 : 2;  // (wide: the message says so, as for POS and CIGAR)
                 out.error_at = (size_t)(line - base);
                 return;
             }
@@ -928,11 +937,24 @@ void tokenize_range(const wk_tok* T, int fmt, const char* base, const char* b, c
                     out.error_at = (size_t)(line - base);
                     return;
                 }
+                if (aligned < 0) {
+                    if (!lens_unread) {
+                        out.error = 4;
+                        out.error_at = (size_t)(line - base);
+                        return;
+                    }
+                    aligned = 0;
+                }
                 if (aligned == 0 && !keep_empty) continue;  // ordinal.py:231 (range.py keeps them)
                 rc.beg = (int32_t)(pos - 1);
                 rc.end = (int32_t)(pos - 1 + span);
                 rc.len = (uint32_t)aligned;
             } else {
+                if (L.neg_len && !lens_unread) {
+                    out.error = 4;
+                    out.error_at = (size_t)(line - base);
+                    return;
+                }
                 if (L.len == 0 && !keep_empty) continue;
                 rc.beg = L.beg;
                 rc.end = L.end;
@@ -1208,12 +1230,13 @@ int wk_tok_text(wk_tok* t, int fmt, const char* buf, int64_t len, int first_bloc
             snprintf(msg, sizeof msg,
                      loc[i].error == 1   ? "SAM flag with both mate bits set in a line of query '%.*s'"
                      : loc[i].error == 3 ? "coordinate wider than 32 bits in a line of query '%.*s'"
+                     : loc[i].error == 4 ? "negative aligned length in a line of query '%.*s'"
                                          : "malformed alignment line of query '%.*s'",
                      qn, ln);
             t->err = msg;
             t->n_loc = 0;
             t->tot_reads = t->tot_rec = t->tot_big = 0;
-            return loc[i].error == 1 ? WK_E_RANGE : WK_E_ARG;
+            return loc[i].error == 1 || loc[i].error == 4 ? WK_E_RANGE : WK_E_ARG;
         }
     for (int i = 0; i < T; ++i) {  // (ranges in text order)
         if (!loc[i].any_run) continue;

@@ -1483,7 +1483,7 @@ class DeviceTextRoute:
             self._host_strata_table()
         res = tok.parse(memoryview(buf).cast('B')[:fill], first=first,
                         final=final, fmt=self._dfmt, want_names=names,
-                        extra=3 if cover else False, want_samples=samples,
+                        extra=7 if cover else False, want_samples=samples,
                         want_groups=groups)
         if samples:
             self._tok_samples.extend(tok.new_samples())
