@@ -87,6 +87,18 @@ int wk_text_clear(wk_ctx* ctx);
  * context was created.  wk_tune "dtok_fused" (0/1) switches it; results never
  * depend on it ("dtok_fused_per_cu": its persistent workgroups per CU). */
 int wk_dtok_fused_counts(wk_ctx* ctx, int64_t* done, int64_t* handed_back);
+/* A timeline of the one-kernel tokenizer.  wk_tune "fz_ablate" bits 2048 and
+ * 4096 leave nothing out (results are the product's): 2048 makes the measuring
+ * instance load every window's text at that window's top instead of a window
+ * ahead; with 4096 thread 0 of every `every`-th workgroup of that instance
+ * stores the wall clock (100 MHz) at the kernel's entry and exit and at the
+ * phases of each window (the layout: csrc/wk_dtok_fused.hpp, kFzTl*).  This
+ * call allocates the buffer where no launch has, waits for the context's
+ * stream and copies the stamps of the last such launch: n_wgs * words_per_wg
+ * words, at most `cap`, to `out`.  The product's instance never writes it. */
+int wk_dtok_fused_timeline(wk_ctx* ctx, uint64_t* out, int64_t cap,
+                           int64_t* n_wgs, int64_t* words_per_wg,
+                           int64_t* every);
 /* Chunks wk_ordinal_count matched sorted by genome stripe (csrc/wk_stripe.hpp)
  * and chunks it matched with the gather kernels alone (csrc/wk_ordinal.hpp),
  * since the context was created.  wk_tune "stripes_min" / WOLTKA_STRIPES_MIN:

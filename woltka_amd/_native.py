@@ -84,7 +84,8 @@ SYMBOLS = (
     'wk_gz_walk_members',
     'wk_gunzip_open', 'wk_gunzip_read', 'wk_gunzip_error', 'wk_gunzip_close',
     'wk_text_upload', 'wk_text_clear', 'wk_h2d_rate',
-    'wk_dtok_fused_counts', 'wk_ordinal_chunk_counts')
+    'wk_dtok_fused_counts', 'wk_ordinal_chunk_counts',
+    'wk_dtok_fused_timeline')
 
 
 class Job(C.Structure):
@@ -342,6 +343,8 @@ def load_library():
         'wk_text_clear': (C.c_int, [p]),
         'wk_dtok_fused_counts': (C.c_int, [p, i64p, i64p]),
         'wk_ordinal_chunk_counts': (C.c_int, [p, i64p, i64p]),
+        'wk_dtok_fused_timeline': (C.c_int, [p, C.c_void_p, C.c_int64, i64p,
+                                             i64p, i64p]),
         'wk_h2d_rate': (C.c_int, [p, C.c_int64, C.c_int,
                                   C.POINTER(C.c_double)]),
     }
@@ -888,6 +891,22 @@ class Context:
         self._check(self._lib.wk_dtok_fused_counts(self._h, C.byref(a),
                                                    C.byref(b)))
         return a.value, b.value
+
+    def dtok_fused_timeline(self):
+        """(measurement) the wall-clock stamps (100 MHz) that the measuring
+        instance of the one-kernel tokenizer left at its last launch with bit
+        4096 of ``fz_ablate``: ``(stamps, every)`` -- a uint64 array of one
+        row per sampled workgroup (every ``every``-th of the grid; the row's
+        layout: csrc/wk_dtok_fused.hpp, kFzTl*)."""
+        n, w, ev = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.wk_dtok_fused_timeline(
+            self._h, None, 0, C.byref(n), C.byref(w), C.byref(ev)))
+        out = np.zeros((n.value, w.value), dtype=np.uint64)
+        if out.size:
+            self._check(self._lib.wk_dtok_fused_timeline(
+                self._h, out.ctypes.data, out.size, C.byref(n), C.byref(w),
+                C.byref(ev)))
+        return out, ev.value
 
     def h2d_rate(self, nbytes=64 << 20, reps=32):
         """(measurement) bytes/s of pinned host -> device copies of

@@ -78,6 +78,29 @@ static_assert(kFzWin + 32 < 65536, "window offsets fit 16 bits");
 constexpr uint32_t kFzCarry = 256;    // mapped lines of a run that goes on behind its window, kept for the windows behind it
 static_assert(kFzCarry + kFzLines <= kFpMaxLines && kFzThreads % kWave == 0, "a window's owned lines fit the planes, a wave's lines one word");
 
+// Bits of FusedArgs::ablate that leave nothing out (the measuring instance gives the product's results with them):
+// 1024 runs that instance as it is; kFzAblateTop has it load every window's text at the window's top, as the kernel
+// did before it loaded a window ahead; kFzAblateTimeline has thread 0 of every kFzTlEvery-th workgroup store the wall
+// clock (100 MHz) into FusedArgs::timeline, a row of kFzTlWords words per sampled workgroup: the kernel's entry, its
+// exit, the windows it walked and its index, then kFzTlPer words for each of its first kFzTlWindows windows.
+constexpr uint32_t kFzAblateTop = 2048, kFzAblateTimeline = 4096;
+constexpr uint32_t kFzTlEvery = 64, kFzTlWindows = 24, kFzTlHead = 4, kFzTlPer = 12;
+constexpr uint32_t kFzTlWords = kFzTlHead + kFzTlWindows * kFzTlPer;
+enum : uint32_t {            // a window's words
+    kFzTlBarrier = 0,        // behind the top barrier: the window before is through with the arrays
+    kFzTlTop,                // the window's loads issued, where they were not a window before
+    kFzTlText,               // the lane's chunks have arrived (behind a wait of this stamp's own)
+    kFzTlStaged,             // behind the barrier that closes staging (text in LDS, newlines counted)
+    kFzTlNumbered,           // behind the barrier that closes the lines' numbering
+    kFzTlProbed,             // the line pass done: tabs, FLAG, RNAME, the dictionary's answers used
+    kFzTlLines,              // behind the line pass's barrier
+    kFzTlAhead,              // the ownership chain done and the next window's loads issued (where there are any)
+    kFzTlPlanes,             // behind the planes' barrier
+    kFzTlEnd,                // the records done: the window's end
+    kFzTlInfo,               // no stamp: mode | the text was loaded a window ahead << 4 | a window follows << 5
+};
+static_assert(kFzTlInfo < kFzTlPer, "a window's words");
+
 constexpr uint32_t kDtokSpill = 64;   // the fused kernel's limits (see above): the unfused kernels take the block
 
 struct FusedArgs {
@@ -104,7 +127,9 @@ struct FusedArgs {
     uint32_t n_submap;
     uint32_t ablate;            // (measurement, wk_tune "fz_ablate": phases left out -- results are wrong then.  Read by
                                 // dtok_fused_measure_kernel alone, which is launched when the word is not 0; bits 1 to 512 are
-                                // tested, so 1024 runs that instance with nothing left out: tests/test_gpu_dtok_instances.py)
+                                // tested, so 1024 runs that instance with nothing left out: tests/test_gpu_dtok_instances.py;
+                                // 2048 and 4096: kFzAblateTop, kFzAblateTimeline)
+    unsigned long long* timeline;   // (measurement) the stamps of kFzAblateTimeline, or null; the product's instance never reads it
 };
 
 // The block's reads (low half) and lines (high half) while the kernel runs: one word behind the DtokState, so that a
@@ -335,7 +360,11 @@ __device__ __forceinline__ uint32_t fz_tabs32(const unsigned char* p, unsigned l
 // The kernel's body.  kMeasure = false is the product's kernel: FusedArgs::ablate is not read and every test of it
 // folds away; kMeasure = true is the measuring instance of tools/fused_ablate.py, with the phases `ablate` names left
 // out at run time (results are wrong then).  Both are instances of this one text: what is measured is what runs.
-template <bool kMeasure>
+// kAhead: the text of the window that follows is asked for as soon as that window is known -- behind the ownership
+// chain, in front of the planes and the records, which never look at txt[] -- into the registers the staging of the
+// next trip reads; only a span's first window loads at its own top.  The measuring instance decides it at run time:
+// bit 2048 of `ablate` = loads at every window's top, as before (like 1024, the bit leaves nothing out).
+template <bool kMeasure, bool kAhead>
 __device__ __forceinline__ void dtok_fused_body(const FusedArgs& a) {
     __shared__ __attribute__((aligned(16))) unsigned char txt[kFzChunks * 16 + 32];
     __shared__ uint16_t ls[kFzLines + 2];                                    // line starts (window offsets); ls[k + 1] - 1 = the newline of line k
@@ -359,6 +388,19 @@ __device__ __forceinline__ void dtok_fused_body(const FusedArgs& a) {
     const uint32_t wave_s = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave);  // (in a scalar register: what depends on it alone is wave-uniform)
     const uint32_t n_streams = a.streams.n_streams;
     const uint32_t ablate = kMeasure ? a.ablate : 0u;
+    const bool ahead = kMeasure ? !(ablate & kFzAblateTop) : kAhead;
+    // (measurement) this workgroup's row of the timeline, where it is a sampled one; thread 0 stamps
+    unsigned long long* tl = nullptr;
+    if (kMeasure && (ablate & kFzAblateTimeline) && a.timeline != nullptr && blockIdx.x % kFzTlEvery == 0u)
+        tl = a.timeline + (size_t)(blockIdx.x / kFzTlEvery) * kFzTlWords;
+    auto stamp = [&](uint32_t word) {
+        if (kMeasure && tl != nullptr && tid == 0) tl[word] = wall_clock64();
+    };
+    auto stamp_window = [&](uint32_t trip_, uint32_t which) {
+        if (kMeasure && trip_ < kFzTlWindows) stamp(kFzTlHead + trip_ * kFzTlPer + which);
+    };
+    stamp(0);
+    if (kMeasure && tl != nullptr && tid == 0) tl[3] = blockIdx.x;
     const int32_t* const submap = a.submap;
     // (the buffers' fill: the word in LDS is added to by the records loop alone; `fill` is what every thread read there
     // behind that loop's barrier, the same in all of them)
@@ -412,6 +454,23 @@ __device__ __forceinline__ void dtok_fused_body(const FusedArgs& a) {
     uint32_t nc = 0u;         // lines in `carry`: the mapped lines so far of a run that began in a window before and has not ended
     uint32_t cq_pos = 0u, cq_len = 0u;  // ... and where its QNAME is in the text
     const uint32_t max_trips = a.span / 16u + 2u;
+    // the end of the text a window looks at, from its first chunk w0_ (one expression for the window's top and for the
+    // loads issued a window ahead: both see the same [w0, w1))
+    auto window_end = [&](uint32_t w0_, uint32_t mode_, bool wide_) {
+        return fr_min_end(mode_ == 0u ? t0 : w0_, mode_ == 0u ? kFzTile + kFzFwd : kFzWin, wide_ ? text_end : span_w1);
+    };
+    // the chunks of this lane for the window [w0_, w1_): all loads under way before the first is looked at; a chunk
+    // behind the window or the text is zeros
+    auto load_window = [&](uint4 (&v_)[kFzRounds], uint32_t w0_, uint32_t w1_, uint32_t c0_, uint32_t rounds_) {
+#pragma unroll
+        for (uint32_t r = 0; r < kFzRounds; ++r) {
+            const uint32_t p = w0_ + (c0_ + r * kWave + lane) * 16u;
+            v_[r] = make_uint4(0u, 0u, 0u, 0u);
+            if (r < rounds_ && p < a.n && p < w1_) v_[r] = fz_load_stream(a.text + p);  // (may pass n: the text's pad)
+        }
+    };
+    uint4 v[kFzRounds];   // the lane's chunks of a window: asked for a window ahead (kAhead) or at the window's top
+    bool loaded = false;  // ... they are under way: the window before asked for them
     for (uint32_t trip = 0;; ++trip) {
         // (never: every window begins at least one whole line behind the one before, or hands a carried run's records
         // over first -- wide windows too, which may follow one another; only a span's first wide look may begin where
@@ -423,10 +482,11 @@ __device__ __forceinline__ void dtok_fused_body(const FusedArgs& a) {
         const uint32_t w0 = wpos & ~15u;
         const uint32_t lead = wpos - w0;  // bytes of the line before in the first chunk (the first window begins at a chunk)
         // text positions [w0, w1) are looked at
-        const uint32_t w1 = fr_min_end(mode == 0u ? t0 : w0, mode == 0u ? kFzTile + kFzFwd : kFzWin, wide ? text_end : span_w1);
+        const uint32_t w1 = window_end(w0, mode, wide);
         const bool to_end = w1 == text_end;   // every line from here to the end of the text is whole
         const bool last_win = wide || w1 == span_w1;  // the span's last window: kFzFwd bytes behind the span, or the end of the text
         __syncthreads();  // (the window before is through with the arrays)
+        stamp_window(trip, kFzTlBarrier);
         // The wave's index once more, as a scalar of this window's own (see the exit for the thread's): what is decided
         // by it below -- the first wave's stores, the rounds a wave runs, the waves in front of it -- is a scalar
         // compare made where it is used.  Compares with `wave_s` itself are the same in every window, and the compiler
@@ -450,13 +510,14 @@ __device__ __forceinline__ void dtok_fused_body(const FusedArgs& a) {
         // the waves of two rounds skip the third, uniformly)
         // (wave_c0 goes into the lanes' addresses, which are kept; ws_c0 is the same number for the scalar tests)
         const uint32_t wave_c0 = fr_first_chunk(wave_s), ws_c0 = fr_first_chunk(ws), wave_rounds = fr_rounds(ws);
-        uint4 v[kFzRounds];
-#pragma unroll
-        for (uint32_t r = 0; r < kFzRounds; ++r) {  // (all loads under way before the first is looked at.  Loading a window ahead, the
-            // registers kept through the window, bought nothing: three workgroups per CU take turns at the memory anyway)
-            const uint32_t p = w0 + (wave_c0 + r * kWave + lane) * 16u;
-            v[r] = make_uint4(0u, 0u, 0u, 0u);
-            if (r < wave_rounds && p < a.n && p < w1) v[r] = fz_load_stream(a.text + p);  // (may pass n: the text's pad)
+        // (a span's first window, and every window where nothing is loaded ahead; the others find their chunks under
+        // way since the window before's ownership chain -- the registers are not written here then)
+        const bool loaded_here = loaded;  // (measurement: for the timeline's info word)
+        if (!loaded) load_window(v, w0, w1, wave_c0, wave_rounds);
+        if (kMeasure && tl != nullptr) {  // (uniform)
+            stamp_window(trip, kFzTlTop);
+            __builtin_amdgcn_s_waitcnt(0x0F70);  // (vmcnt(0): the staging below would wait here for its first chunk anyway)
+            stamp_window(trip, kFzTlText);
         }
         uint32_t marks[kFzRounds];
         uint32_t nl_packed = 0;
@@ -500,6 +561,7 @@ __device__ __forceinline__ void dtok_fused_body(const FusedArgs& a) {
         const uint32_t nl_wave = fz_last_lane(nl_inc);
         if (lane == 0) wtot[wave] = fr_total(nl_wave);
         __syncthreads();
+        stamp_window(trip, kFzTlStaged);
         // (the waves' counts as scalars -- every lane reads the same words --, so that "the waves in front" is a scalar
         // compare with the wave's index and no mask of threads is kept through the window for it)
         uint32_t before = 0, total_nl = 0;
@@ -532,6 +594,7 @@ __device__ __forceinline__ void dtok_fused_body(const FusedArgs& a) {
             }
         }
         __syncthreads();
+        stamp_window(trip, kFzTlNumbered);
         // A line that STARTS in this span and does not end inside the span's last window is a line nobody sees whole:
         // its span is the one that would own a run it starts, and the spans behind it find no run start in it.  (Lines
         // of more than kFzFwd bytes -- SEQ / QUAL of a long read kept; text that comes through the column trim has
@@ -664,7 +727,9 @@ __device__ __forceinline__ void dtok_fused_body(const FusedArgs& a) {
                 atomicMax(&own[2], k + 63u - (uint32_t)__builtin_clzll(b_all));
             }
         }
+        stamp_window(trip, kFzTlProbed);
         __syncthreads();
+        stamp_window(trip, kFzTlLines);
         // ---- what the lane below did not settle: the search back ----
         // (What every mapped line used to do: the mapped line before it searched for, the QNAMEs compared byte by byte.
         // own[4], read behind the barrier and the same in every thread, says whether any wave holds such a line: text
@@ -789,6 +854,22 @@ __device__ __forceinline__ void dtok_fused_body(const FusedArgs& a) {
                 again = last_win;
             }
         }
+        // ---- the next window's text asked for (kAhead) ----
+        // The window that follows is fixed here, and everything from here to its staging works on info[], planes[],
+        // rbuf[] and the buffers' fill, never on txt[] or on `v`: its chunks travel under the duplicate walk, the
+        // planes, the records and the next window's top.  The same chunks, limits and predicate as a load at that
+        // top: `next` becomes wpos, `next_mode` (never 0) mode, `again` wide.
+        // (vmcnt(0), said out loud: every load of the line pass has been used by now, but the compiler's bookkeeping
+        // keeps some of their registers "under way" along paths that drop them, and where such a path meets this one
+        // they count as younger than the loads below -- the planes' and the records' first writes to those registers
+        // would wait for the text.  Nothing is under way here, so this wait costs nothing.)
+        __builtin_amdgcn_s_waitcnt(0x0F70);
+        loaded = ahead && more;
+        if (loaded) {  // (uniform)
+            const uint32_t w0n = next & ~15u;
+            load_window(v, w0n, window_end(w0n, next_mode, again), wave_c0, wave_rounds);
+        }
+        stamp_window(trip, kFzTlAhead);
         // ---- first line of its read (run, mate) that names its subject (the plain parsers keep sets, align.py:309) ----
         // (walks read eight lines' words at a time: one trip to the LDS per eight lines instead of two per line.)  What
         // the lanes find leaves as the planes' words: a wave's 64 lines are one word of each plane, a ballot each -- so
@@ -830,6 +911,7 @@ __device__ __forceinline__ void dtok_fused_body(const FusedArgs& a) {
             }
         }
         __syncthreads();
+        stamp_window(trip, kFzTlPlanes);
         // ---- records: position and size inside the read ----
         for (int32_t k0 = ka; k0 < kb; k0 += (int32_t)kFzThreads) {  // (uniform trip count: barriers inside)
             const int32_t k = k0 + (int32_t)tid;
@@ -896,6 +978,11 @@ __device__ __forceinline__ void dtok_fused_body(const FusedArgs& a) {
             // 0's store above and the next add.)
             if (k0 + (int32_t)kFzThreads < kb) __syncthreads();
         }
+        stamp_window(trip, kFzTlEnd);
+        if (kMeasure && tl != nullptr && tid == 0) {
+            tl[2] = trip + 1u;
+            if (trip < kFzTlWindows) tl[kFzTlHead + trip * kFzTlPer + kFzTlInfo] = mode | (loaded_here ? 16u : 0u) | (more ? 32u : 0u);
+        }
         if (!more) break;
         wpos = next;
         mode = next_mode;
@@ -952,15 +1039,16 @@ __device__ __forceinline__ void dtok_fused_body(const FusedArgs& a) {
             if (a.host_seq) __hip_atomic_store(a.host_seq, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
+    stamp(1);
 }
 
 // the product's kernel
 __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu(6, 6))) dtok_fused_kernel(FusedArgs a) {
-    dtok_fused_body<false>(a);
+    dtok_fused_body<false, true>(a);
 }
 // the same with the measurement switches of wk_tune "fz_ablate" (launched exactly when that word is not 0)
 __global__ void __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu(6, 6))) dtok_fused_measure_kernel(FusedArgs a) {
-    dtok_fused_body<true>(a);
+    dtok_fused_body<true, true>(a);
 }
 
 }  // namespace wk

@@ -372,6 +372,8 @@ struct wk_ctx {
     unsigned long long* copy_newlines = nullptr;   // [kTextBufs], behind the slots of host_back
     uint32_t* di_any_host = nullptr;               // [kTextBufs], allocated by the first wk_dtok_inflate_ahead
     DevBuf d_tiles, d_tile_off, d_lines, d_lsubj, d_lmeta, d_start, d_first, d_unknown, d_state, d_dict, d_dict2, d_names16, d_arena, d_submap;
+    DevBuf d_timeline;         // (measurement, wk_dtok_fused_timeline) the stamps of the measuring instance's sampled workgroups
+    uint32_t tl_wgs = 0;       // ... of the launch that wrote them last: its sampled workgroups
     bool dt_mapped = false;       // the block scanned last has had its lines' ids translated (dtok_submap_kernel)
     bool dt_submap_on = false;    // a map has been given (it may be empty still)
     bool dt_has_excl = false;     // the map holds kLineExcluded: `--exclude` on the device text route
@@ -1170,7 +1172,7 @@ void wk_destroy(wk_ctx* c) {
     }
     for (DevBuf& slab : c->d_textslab) slab.release();
     for (DevBuf* b : {&c->d_tiles, &c->d_tile_off, &c->d_lines, &c->d_lsubj, &c->d_lmeta, &c->d_start, &c->d_first, &c->d_unknown, &c->d_lbeg, &c->d_lend, &c->d_llen, &c->d_lscan, &c->d_gmap,
-                      &c->d_state, &c->d_dict, &c->d_dict2, &c->d_names16, &c->d_arena, &c->d_submap, &c->cv_key[0], &c->cv_key[1], &c->cv_end[0], &c->cv_end[1],
+                      &c->d_state, &c->d_timeline, &c->d_dict, &c->d_dict2, &c->d_names16, &c->d_arena, &c->d_submap, &c->cv_key[0], &c->cv_key[1], &c->cv_end[0], &c->cv_end[1],
                       &c->cv_reach, &c->cv_hist, &c->cv_tiles, &c->cv_tile_off, &c->cv_state, &c->cv_stage[0], &c->cv_stage[1], &c->cv_stage[2],
                       &c->dx_tab, &c->dx_name_off, &c->dx_arena, &c->dx_group, &c->dx_met, &c->dx_pend, &c->dx_pend_list, &c->dx_state, &c->dx_lsamp, &c->dx_out, &c->dx_rsamp,
                       &c->rr_off, &c->rr_text, &c->rr_flags})
@@ -3643,6 +3645,25 @@ int wk_dtok_fused_counts(wk_ctx* c, int64_t* done, int64_t* handed_back) {
     return WK_OK;
 }
 
+// (measurement) The stamps the measuring instance of the one-kernel tokenizer left at its last launch with bit 4096 of
+// "fz_ablate" (wk_dtok_fused.hpp, kFzTl*): the buffer is made here where no such launch has made it, the context's
+// stream is waited for, and up to `cap` words go to `out`.
+int wk_dtok_fused_timeline(wk_ctx* c, uint64_t* out, int64_t cap, int64_t* n_wgs, int64_t* words_per_wg, int64_t* every) {
+    if (!c || !n_wgs || !words_per_wg || !every || cap < 0 || (cap > 0 && !out)) return WK_E_ARG;
+    DeviceGuard guard(c->device);
+    if (!c->d_timeline.p) {
+        HIP_TRY(c, c->d_timeline.reserve((size_t)16 * kFzTlWords * 8));
+        HIP_TRY(c, hipMemsetAsync(c->d_timeline.p, 0, c->d_timeline.cap, c->stream));
+    }
+    *n_wgs = c->tl_wgs;
+    *words_per_wg = kFzTlWords;
+    *every = kFzTlEvery;
+    const int64_t have = (int64_t)c->tl_wgs * (int64_t)kFzTlWords, take = std::min(have, cap);
+    if (take > 0) HIP_TRY(c, hipMemcpyAsync(out, c->d_timeline.p, (size_t)take * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return WK_OK;
+}
+
 int wk_text_clear(wk_ctx* c) {
     if (!c) return WK_E_ARG;
     DeviceGuard guard(c->device);
@@ -3774,6 +3795,14 @@ static int fused_launch(wk_ctx* c, const StreamSet& streams, const unsigned char
     fa.submap = c->dt_submap_on ? c->d_submap.as<int32_t>() : nullptr;
     fa.n_submap = c->dt_submap_n;
     fa.ablate = c->fused_ablate;
+    fa.timeline = nullptr;  // (the product's instance never reads it)
+    if (c->fused_ablate & kFzAblateTimeline) {  // (measurement: the buffer cleared in front of every launch that stamps)
+        const uint32_t wgs = (grid + kFzTlEvery - 1u) / kFzTlEvery;
+        HIP_TRY(c, c->d_timeline.reserve((size_t)std::max(wgs, 16u) * kFzTlWords * 8));
+        HIP_TRY(c, hipMemsetAsync(c->d_timeline.p, 0, (size_t)wgs * kFzTlWords * 8, c->stream));
+        fa.timeline = c->d_timeline.as<unsigned long long>();
+        c->tl_wgs = wgs;
+    }
     c->w_counts_known = false;
     KernelTimer* kf = ktimer_begin(c, "dtok_fused");
     if (!c->fz_chain)
