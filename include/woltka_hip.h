@@ -669,6 +669,32 @@ int wk_readmap_reads_tables(wk_ctx* ctx, int32_t first, int32_t n,
                             const uint32_t* shown_off, const char* shown);
 int wk_dtok_readmap_reads(wk_ctx* ctx, int32_t job, int64_t* n_bytes);
 
+/* Read maps with taxon lists on the device (csrc/wk_readmap_lists.hpp):
+ * `--outmap` for job sets that hold a job able to split a read over several
+ * features -- none without --uniq, a plain rank without --uniq / --above /
+ * --major (classify.py:32-51, 81-127) -- so that a line is
+ * `query[/mate] <tab> taxon:count <tab> taxon:count ...`, by count descending,
+ * then by the taxon id's bytes (file.write_readmap, file.py:469-500).
+ *   wk_dtok_readmap_lists  wk_dtok_readmap_reads for any kind of job: a code
+ *                      that is a feature or WK_ASSIGN_NONE is printed the same
+ *                      way, WK_ASSIGN_MULTI as the list of the read's distinct
+ *                      subjects' features (none) or ancestors at the job's rank
+ *                      (subjects without one are dropped).  --unassigned does
+ *                      not touch a list.  *n_bytes = the size of the text;
+ *                      wk_dtok_readmap_fetch copies it out.  WK_E_STATE if a
+ *                      code is "no candidates" or a feature lies outside the
+ *                      shown-text table: no text then.
+ *   wk_readmap_lists_ids  the bytes the lists are ordered by: the ids of
+ *                      features [first, first + n), set and extended like
+ *                      wk_readmap_reads_tables.  Needed only when the shown
+ *                      text is not the id (--name-as-id); without it the shown
+ *                      text is the order.  It must cover the features the
+ *                      shown-text table covers; setting that table anew
+ *                      (first = 0) forgets the ids. */
+int wk_dtok_readmap_lists(wk_ctx* ctx, int32_t job, int64_t* n_bytes);
+int wk_readmap_lists_ids(wk_ctx* ctx, int32_t first, int32_t n,
+                         const uint32_t* id_off, const char* ids);
+
 /* Convenience: stage + classify in one call from host buffers. */
 int wk_classify_chunk(wk_ctx* ctx, const wk_job* jobs, int32_t n_jobs,
                       const int32_t* subj, const int32_t* qoff,

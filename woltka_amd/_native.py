@@ -68,6 +68,7 @@ SYMBOLS = (
     'wk_dtok_stage_reads_strata', 'wk_chunk_groups',
     'wk_dtok_stage_reads_plain', 'wk_classify_staged_keep',
     'wk_readmap_reads_tables', 'wk_dtok_readmap_reads',
+    'wk_dtok_readmap_lists', 'wk_readmap_lists_ids',
     'wk_tok_subjects',
     'wk_tok_new_subjects', 'wk_tok_fetch_groups', 'wk_tok_strata_clear',
     'wk_tok_strata_load', 'wk_tok_strata_labels', 'wk_tok_strata_select',
@@ -285,6 +286,9 @@ def load_library():
         'wk_readmap_reads_tables': (C.c_int, [p, C.c_int32, C.c_int32, u32p,
                                               C.c_void_p]),
         'wk_dtok_readmap_reads': (C.c_int, [p, C.c_int32, i64p]),
+        'wk_dtok_readmap_lists': (C.c_int, [p, C.c_int32, i64p]),
+        'wk_readmap_lists_ids': (C.c_int, [p, C.c_int32, C.c_int32, u32p,
+                                           C.c_void_p]),
         'wk_tok_subjects': (C.c_int, [p, i32p, i32p, i64p]),
         'wk_tok_new_subjects': (C.c_int, [p, C.c_char_p, i32p]),
         'wk_tok_fetch_groups': (C.c_int, [p, i32p]),
@@ -1192,6 +1196,35 @@ class Context:
         whether it lies in ``out``."""
         n = C.c_int64(0)
         self._check(self._lib.wk_dtok_readmap_reads(self._h, int(job),
+                                                    C.byref(n)))
+        inside = out is not None and out.size >= n.value
+        if not inside:
+            out = np.empty(n.value, dtype=np.uint8)
+        if n.value:
+            self._check(self._lib.wk_dtok_readmap_fetch(
+                self._h, C.c_void_p(out.ctypes.data), out.size))
+        return out[:n.value], inside
+
+    # -- read maps with taxon lists (csrc/wk_readmap_lists.hpp) --
+    def readmap_lists_ids(self, first, blob, off):
+        """The bytes the lists of ``dtok_readmap_lists`` are ordered by: the
+        ids of features ``first`` .. ``first + off.size - 1``, in the layout of
+        ``readmap_reads_tables`` and set or extended like it.  Only needed
+        when the shown text is not the id."""
+        off = _arr(off, np.uint32)
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        if off.size < 1 or int(off[-1]) != blob.size:
+            raise ValueError('offsets must run from 0 to the size of the text')
+        self._check(self._lib.wk_readmap_lists_ids(
+            self._h, int(first), off.size - 1, _ptr(off, C.c_uint32),
+            C.c_void_p(blob.ctypes.data if blob.size else 0)))
+
+    def dtok_readmap_lists(self, job, out=None):
+        """``dtok_readmap_reads`` for any kind of job: a read the job split
+        over several features is printed as its list, ``taxon:count`` by count
+        descending, then id."""
+        n = C.c_int64(0)
+        self._check(self._lib.wk_dtok_readmap_lists(self._h, int(job),
                                                     C.byref(n)))
         inside = out is not None and out.size >= n.value
         if not inside:

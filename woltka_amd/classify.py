@@ -273,6 +273,9 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
         # read maps of whole-read assignments formatted on the device (csrc/wk_readmap_reads.hpp)
         self._dreadmaps = None      # (rank2dir, outzip, namedic) while a file is read that way
         self._shown_sent = None     # (namedic, features) the device's shown-text table covers
+        # ... of sets with a job that returns lists (csrc/wk_readmap_lists.hpp)
+        self._dlists = False        # `_dreadmaps` is read by `_run_dreads_lists`: its blocks are 'dreads_lists'
+        self._ids_sent = 0          # features the device's id table covers (the lists' order under --name-as-id)
         self._sbuf = [None, None]   # pinned buffers the map text is inflated into
         self._sbuf_next = 0
 
@@ -437,7 +440,7 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
                       fmt='sam', part=None, words=False, dmaps=None,
                       keep_empty=False, words_dev=False, dcover=False,
                       ddemux=None, dreads=False, dhdemux=None,
-                      dreadmaps=None):
+                      dreadmaps=None, dlistmaps=None):
         """SAM text -> packed chunks through the native tokenizer.  Yields
         (reads or None, packed, strata ids, name descriptors, sample ids,
         ranges) where packed = (subj, qoff) of subject indices, or for
@@ -461,7 +464,11 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
         ``dreadmaps`` (`read_maps_on_device`): (rank2dir, outzip, namedic) --
         plain classification with read maps of a set in which no job returns
         a list: the blocks are counted as CSR chunks, the codes stay on the
-        device and the maps are formatted there (`_run_dreads_maps`)."""
+        device and the maps are formatted there (`_run_dreads_maps`).
+        ``dlistmaps`` (`read_map_lists_on_device`): the same triple for a set
+        in which a job can return a list, asked when neither ``dmaps`` nor
+        ``dreadmaps`` took the file: the same blocks, the maps formatted by
+        the list formatter (`_run_dreads_lists`)."""
         from .align import native_sam_blocks
         if self.tok is None:
             # (a tokenizer whose dictionary was filled from this file's first
@@ -500,6 +507,14 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
             not ordinal and cover is None and not want_groups and
             not want_samples and part is None and
             len(self.jobs) <= nat.MAX_JOBS) else None
+        dlists = False
+        if dreadmaps is None and dlistmaps is not None and not (
+                words or words_dev or dmaps or ordinal or want_groups or
+                want_samples) and cover is None and part is None and \
+                len(self.jobs) <= nat.MAX_JOBS:
+            # (the blocks are staged, counted and fetched the same way: only
+            # the formatter differs)
+            dreadmaps, dlists = dlistmaps, True
         if (words or words_dev or device_ex or dmaps or dcover or
                 ddemux is not None or dreads or dreadmaps is not None) and (
                 fmt in ('sam', 'b6o', 'paf') or (fmt == 'map' and
@@ -534,6 +549,7 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
                 self._ddemux = ddemux
                 self._dreads = dreads
                 self._dreadmaps = dreadmaps
+                self._dlists = dlists
                 self._dhdemux = dhdemux if device_ex else None
                 if ddemux is not None or dreads or dreadmaps is not None or \
                         self._dhdemux is not None:
@@ -576,6 +592,7 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
                     self._dhdemux = None
                     self._dreads = False
                     self._dreadmaps = None
+                    self._dlists = False
                     if getattr(self.ctx, '_h', None):   # (still open)
                         self.ctx.dtok_keep_reads(False)
                 return
@@ -812,6 +829,7 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
                 'ddemux': '_run_ddemux',    # text scanned on the device -> demultiplexed CSR chunk, counted by the general evaluator
                 'dreads': '_run_dstrata_reads',     # ... -> CSR chunk with the reads' strata joined on the device, counted likewise
                 'dreads_maps': '_run_dreads_maps',  # ... -> CSR chunk of one group, counted likewise, read maps formatted from the codes on the device
+                'dreads_lists': '_run_dreads_lists',    # ... the same for a set with a job that returns lists
                 'words': '_run_words'}      # packed records of the host tokenizer (routes/words.py)
 
     def _run_general(self, data, reads, subque, sample_of, strata_of, trimsub,

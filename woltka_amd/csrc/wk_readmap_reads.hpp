@@ -62,11 +62,8 @@ __device__ __forceinline__ uint32_t readmap_reads_shown(const ReadmapReadsArgs& 
     return 0u;
 }
 
-// a thread per read: the length of its line (0: none)
-__global__ void __launch_bounds__(kDtokThreads) readmap_reads_len_kernel(DtokArgs a, ReadmapReadsArgs m) {
-    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= m.n_reads) return;
-    const int32_t v = m.assign[r];
+// The length of read r's line under code v (0: none)
+__device__ __forceinline__ unsigned long long readmap_reads_line_len(const DtokArgs& a, const ReadmapReadsArgs& m, uint32_t r, int32_t v) {
     const uint32_t i = m.read_line[r];
     unsigned long long len = 0;
     // (a feature with an empty id still has its line: only "nothing" has none)
@@ -76,14 +73,18 @@ __global__ void __launch_bounds__(kDtokThreads) readmap_reads_len_kernel(DtokArg
         const uint32_t meta = a.lmeta[i];
         len = (unsigned long long)(meta & 0x0FFFFFFFu) + ((meta >> 28) ? 2u : 0u) + 1u + shown + 1u;
     }
-    m.read_len[r] = len;
+    return len;
 }
 
-// a thread per read: its line at read_len[r] (now the exclusive prefix)
-__global__ void __launch_bounds__(kDtokThreads) readmap_reads_write_kernel(DtokArgs a, ReadmapReadsArgs m) {
+// a thread per read: the length of its line
+__global__ void __launch_bounds__(kDtokThreads) readmap_reads_len_kernel(DtokArgs a, ReadmapReadsArgs m) {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= m.n_reads) return;
-    const int32_t v = m.assign[r];
+    m.read_len[r] = readmap_reads_line_len(a, m, r, m.assign[r]);
+}
+
+// Read r's line under code v at read_len[r] (now the exclusive prefix)
+__device__ __forceinline__ void readmap_reads_write_line(const DtokArgs& a, const ReadmapReadsArgs& m, uint32_t r, int32_t v) {
     const uint32_t i = m.read_line[r];
     if (i >= a.n_lines) return;
     const unsigned char* s;
@@ -112,6 +113,13 @@ __global__ void __launch_bounds__(kDtokThreads) readmap_reads_write_kernel(DtokA
     for (uint32_t k = 0; k < n; ++k) o[at + k] = s[k];
     at += n;
     o[at] = '\n';
+}
+
+// a thread per read: its line
+__global__ void __launch_bounds__(kDtokThreads) readmap_reads_write_kernel(DtokArgs a, ReadmapReadsArgs m) {
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= m.n_reads) return;
+    readmap_reads_write_line(a, m, r, m.assign[r]);
 }
 
 }  // namespace wk

@@ -31,6 +31,7 @@
 #include "wk_stripe.hpp"
 #include "wk_readmap.hpp"
 #include "wk_readmap_reads.hpp"
+#include "wk_readmap_lists.hpp"
 #include "wk_tok_internal.h"
 #include "wk_weigh.hpp"
 #include "wk_weigh_wide.hpp"
@@ -468,6 +469,13 @@ struct wk_ctx {
     int64_t rr_serial = -1;       // stage_serial of the chunk whose codes assign_out holds ...
     int32_t rr_jobs = 0;          // ... and the jobs they were written for
     uint32_t rr_unassigned = 0;   // ... under --unassigned
+    // read maps with taxon lists (wk_readmap_lists.hpp): the id table the lists are ordered by when the shown text is
+    // not the id, the lists' pairs; the kind of every job the codes were written for
+    DevBuf rl_off, rl_text, rl_pairs, rl_npairs;
+    int32_t rl_n = 0;             // features the id table covers (0: the shown text is the id)
+    uint32_t rl_text_n = 0;
+    int32_t rl_mode[WK_MAX_JOBS] = {};
+    int32_t rl_slot[WK_MAX_JOBS] = {};
     int range_parts_opt = 0;   // partitions of the dense gene log (0: as few as the merge's LDS array allows; measurement)
     int use_streams = 1;   // (0: the records of all slices in one stream, round 3's team kernel; measurement)
     int use_subject_bins = 1;
@@ -1175,7 +1183,8 @@ void wk_destroy(wk_ctx* c) {
                       &c->d_state, &c->d_timeline, &c->d_dict, &c->d_dict2, &c->d_names16, &c->d_arena, &c->d_submap, &c->cv_key[0], &c->cv_key[1], &c->cv_end[0], &c->cv_end[1],
                       &c->cv_reach, &c->cv_hist, &c->cv_tiles, &c->cv_tile_off, &c->cv_state, &c->cv_stage[0], &c->cv_stage[1], &c->cv_stage[2],
                       &c->dx_tab, &c->dx_name_off, &c->dx_arena, &c->dx_group, &c->dx_met, &c->dx_pend, &c->dx_pend_list, &c->dx_state, &c->dx_lsamp, &c->dx_out, &c->dx_rsamp,
-                      &c->rr_off, &c->rr_text, &c->rr_flags})
+                      &c->rr_off, &c->rr_text, &c->rr_flags,
+                      &c->rl_off, &c->rl_text, &c->rl_pairs, &c->rl_npairs})
         b->release();
     for (wk_ctx::ResidentText& r : c->resident) {
         (void)hipFree(r.dev);
@@ -1795,6 +1804,10 @@ int wk_classify_staged_keep(wk_ctx* c, const wk_job* jobs, int32_t n_jobs) {
     c->rr_serial = c->stage_serial;
     c->rr_jobs = n_jobs;
     c->rr_unassigned = (jobs[0].flags & WK_F_UNASSIGNED) ? 1u : 0u;
+    for (int j = 0; j < n_jobs; ++j) {
+        c->rl_mode[j] = jobs[j].mode;
+        c->rl_slot[j] = jobs[j].rank_slot;
+    }
     return WK_OK;
 }
 
@@ -5631,29 +5644,43 @@ int wk_dtok_stage_reads_plain(wk_ctx* c, int64_t* n_reads, int64_t* n_records, i
     return stage_reads_chunk(c, kStagePlain, n_reads, n_records, status);
 }
 
-int wk_readmap_reads_tables(wk_ctx* c, int32_t first, int32_t n, const uint32_t* shown_off, const char* shown) {
-    if (!c) return WK_E_ARG;
-    if (first < 0 || n < 0 || (n > 0 && !shown_off)) return fail(c, WK_E_ARG, "bad shown-text table");
-    if (first != 0 && first != c->rr_n) return fail(c, WK_E_ARG, "the shown-text table holds %d features: set it from 0 or extend it from there", c->rr_n);
+// A text table over the feature ids (features [first, first + n) hold text[off[k], off[k + 1])): set from 0 or extended
+// from its size `have`, whose text ends at `have_text`.
+static int text_table_set(wk_ctx* c, const char* what, DevBuf& d_off, DevBuf& d_text, int32_t& have, uint32_t& have_text, int32_t first, int32_t n,
+                          const uint32_t* shown_off, const char* shown) {
+    if (first < 0 || n < 0 || (n > 0 && !shown_off)) return fail(c, WK_E_ARG, "bad %s table", what);
+    if (first != 0 && first != have) return fail(c, WK_E_ARG, "the %s table holds %d features: set it from 0 or extend it from there", what, have);
     if (n > 0 && shown_off[0] != 0) return fail(c, WK_E_ARG, "shown_off must start at 0");
     for (int32_t k = 0; k < n; ++k)
         if (shown_off[k + 1] < shown_off[k]) return fail(c, WK_E_ARG, "shown_off must not decrease");
     const uint32_t n_text = n > 0 ? shown_off[n] : 0u;
-    if (n_text > 0 && !shown) return fail(c, WK_E_ARG, "bad shown-text table");
-    const uint32_t base = first ? c->rr_text_n : 0u;
-    if ((uint64_t)base + n_text >= (1ull << 32) || (int64_t)first + n >= (1ll << 31)) return fail(c, WK_E_RANGE, "shown-text table beyond 2^32 bytes");
+    if (n_text > 0 && !shown) return fail(c, WK_E_ARG, "bad %s table", what);
+    const uint32_t base = first ? have_text : 0u;
+    if ((uint64_t)base + n_text >= (1ull << 32) || (int64_t)first + n >= (1ll << 31)) return fail(c, WK_E_RANGE, "%s table beyond 2^32 bytes", what);
     DeviceGuard guard(c->device);
     HIP_TRY(c, hipStreamSynchronize(c->stream));  // (a kernel may be reading the table that is there)
-    HIP_TRY(c, grow_keep(c, c->rr_off, ((size_t)first + n + 1) * 4, first ? ((size_t)first + 1) * 4 : 0));
-    HIP_TRY(c, grow_keep(c, c->rr_text, (size_t)base + n_text + 64, base));
+    HIP_TRY(c, grow_keep(c, d_off, ((size_t)first + n + 1) * 4, first ? ((size_t)first + 1) * 4 : 0));
+    HIP_TRY(c, grow_keep(c, d_text, (size_t)base + n_text + 64, base));
     std::vector<uint32_t> off((size_t)n + 1);
     for (int32_t k = 0; k <= n; ++k) off[k] = base + (n > 0 ? shown_off[k] : 0u);
-    HIP_TRY(c, hipMemcpyAsync(c->rr_off.as<uint32_t>() + first, off.data(), off.size() * 4, hipMemcpyHostToDevice, c->stream));
-    if (n_text) HIP_TRY(c, hipMemcpyAsync(c->rr_text.as<unsigned char>() + base, shown, n_text, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_off.as<uint32_t>() + first, off.data(), off.size() * 4, hipMemcpyHostToDevice, c->stream));
+    if (n_text) HIP_TRY(c, hipMemcpyAsync(d_text.as<unsigned char>() + base, shown, n_text, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));  // (the caller's buffers are only valid during the call)
-    c->rr_n = first + n;
-    c->rr_text_n = base + n_text;
+    have = first + n;
+    have_text = base + n_text;
     return WK_OK;
+}
+
+int wk_readmap_reads_tables(wk_ctx* c, int32_t first, int32_t n, const uint32_t* shown_off, const char* shown) {
+    if (!c) return WK_E_ARG;
+    const int rc = text_table_set(c, "shown-text", c->rr_off, c->rr_text, c->rr_n, c->rr_text_n, first, n, shown_off, shown);
+    if (rc == WK_OK && first == 0) c->rl_n = 0;  // (a new table: the ids of the one before say nothing about it)
+    return rc;
+}
+
+int wk_readmap_lists_ids(wk_ctx* c, int32_t first, int32_t n, const uint32_t* id_off, const char* ids) {
+    if (!c) return WK_E_ARG;
+    return text_table_set(c, "id", c->rl_off, c->rl_text, c->rl_n, c->rl_text_n, first, n, id_off, ids);
 }
 
 int wk_dtok_readmap_reads(wk_ctx* c, int32_t job, int64_t* n_bytes) {
@@ -5709,6 +5736,92 @@ int wk_dtok_readmap_reads(wk_ctx* c, int32_t job, int64_t* n_bytes) {
         m.out = c->rm_text.as<unsigned char>();
         m.out_cap = total;
         hipLaunchKernelGGL(readmap_reads_write_kernel, rgrid, dim3(kDtokThreads), 0, c->stream, a, m);
+        HIP_TRY(c, hipGetLastError());
+    }
+    ktimer_end(c, kt);
+    c->rm_bytes = (int64_t)total;
+    *n_bytes = (int64_t)total;
+    return WK_OK;
+}
+
+// ---- read maps with taxon lists on the device (wk_readmap_lists.hpp) ---------------------------------------------
+
+int wk_dtok_readmap_lists(wk_ctx* c, int32_t job, int64_t* n_bytes) {
+    if (!c || !n_bytes) return WK_E_ARG;
+    *n_bytes = 0;
+    c->rm_bytes = 0;
+    if (!c->rr_chunk || !c->chunk_valid) return fail(c, WK_E_STATE, "no chunk staged by wk_dtok_stage_reads_plain");
+    if (c->rr_serial != c->stage_serial) return fail(c, WK_E_STATE, "the staged chunk's codes are not on the device (wk_classify_staged_keep)");
+    if (job < 0 || job >= c->rr_jobs) return fail(c, WK_E_ARG, "job must be in [0, %d)", c->rr_jobs);
+    if (c->n_reads >= (1ll << 32) - 1 || c->n_records >= (1ll << 31)) return fail(c, WK_E_RANGE, "more than 2^31 records in one block");
+    if (c->rl_n != 0 && c->rl_n != c->rr_n)
+        return fail(c, WK_E_STATE, "the id table holds %d features, the shown-text table %d (wk_readmap_lists_ids)", c->rl_n, c->rr_n);
+    const uint32_t n_reads = (uint32_t)c->n_reads;
+    if (n_reads == 0 || c->dt_lines == 0) return WK_OK;
+    const int32_t* anc = nullptr;
+    if (c->rl_mode[job] == WK_MODE_RANK) {
+        const int slot = c->rl_slot[job];
+        if (slot < 0 || slot >= (int)(sizeof c->rank_tab / sizeof c->rank_tab[0]) || !c->rank_tab_valid[slot])
+            return fail(c, WK_E_STATE, "job %d: rank slot %d has not been built", job, slot);
+        anc = c->rank_tab[slot].as<int32_t>();
+    }
+    DeviceGuard guard(c->device);
+    KtScope kt_scope(c);
+    HIP_TRY(c, c->rm_len.reserve((size_t)n_reads * 8));
+    HIP_TRY(c, c->rr_flags.reserve(16));
+    HIP_TRY(c, c->rr_off.reserve(4));  // (an empty table still has its first offset's place)
+    HIP_TRY(c, c->rl_pairs.reserve((size_t)std::max<int64_t>(c->n_records, 1) * sizeof(uint2)));
+    HIP_TRY(c, c->rl_npairs.reserve((size_t)n_reads * 4));
+    DtokArgs a = dtok_args(c);
+    ReadmapListsArgs L{};
+    ReadmapReadsArgs& m = L.m;
+    m.assign = c->assign_out.as<int32_t>() + (size_t)job * n_reads;
+    m.read_line = c->rm_line.as<uint32_t>();
+    m.shown_off = c->rr_off.as<uint32_t>();
+    m.shown = c->rr_text.as<unsigned char>();
+    m.n_shown = (uint32_t)c->rr_n;
+    m.read_len = c->rm_len.as<unsigned long long>();
+    m.flags = c->rr_flags.as<uint32_t>();
+    m.n_reads = n_reads;
+    m.unassigned = c->rr_unassigned;
+    L.subj = c->cur_subj;
+    L.qoff = c->cur_qoff;
+    L.subj_feat = c->subj_feat.as<int32_t>();
+    L.n_subjects = (uint32_t)std::max(c->n_subjects, 0);
+    L.anc = anc;
+    L.n_nodes = (uint32_t)std::max(c->n_nodes, 0);
+    L.key_off = c->rl_n ? c->rl_off.as<uint32_t>() : m.shown_off;
+    L.key = c->rl_n ? c->rl_text.as<unsigned char>() : m.shown;
+    L.pairs = c->rl_pairs.as<uint2>();
+    L.n_pairs = c->rl_npairs.as<uint32_t>();
+    const dim3 rgrid((n_reads + kDtokThreads - 1) / kDtokThreads);
+    HIP_TRY(c, c->d_tiles.reserve((size_t)rgrid.x * 8));
+    HIP_TRY(c, c->d_tile_off.reserve((size_t)rgrid.x * 8));
+    HIP_TRY(c, hipMemsetAsync(c->rr_flags.p, 0, 16, c->stream));
+    HIP_TRY(c, hipMemsetAsync(scalar_u64(c, 3), 0, 8, c->stream));
+    KernelTimer* kt = ktimer_begin(c, "readmap_lists");
+    hipLaunchKernelGGL(readmap_lists_build_kernel, rgrid, dim3(kDtokThreads), 0, c->stream, a, L);
+    hipLaunchKernelGGL(u64_tile_sum_kernel, rgrid, dim3(kDtokThreads), 0, c->stream, m.read_len, n_reads, c->d_tiles.as<unsigned long long>());
+    hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_tiles.as<unsigned long long>(),
+                       c->d_tile_off.as<unsigned long long>(), (int64_t)rgrid.x, scalar_u64(c, 3));
+    hipLaunchKernelGGL(u64_tile_prefix_kernel, rgrid, dim3(kDtokThreads), 0, c->stream, m.read_len, n_reads, c->d_tile_off.as<unsigned long long>());
+    HIP_TRY(c, hipGetLastError());
+    unsigned long long total = 0;
+    uint32_t flags = 0;
+    HIP_TRY(c, hipMemcpyAsync(&total, scalar_u64(c, 3), 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&flags, c->rr_flags.p, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (flags) {
+        ktimer_end(c, kt);
+        return fail(c, WK_E_STATE, "job %d left a code or a list that the tables cannot print (%d features shown, %d subjects)", job, c->rr_n,
+                    c->n_subjects);
+    }
+    if (total >= (1ull << 40)) return fail(c, WK_E_RANGE, "read-map text of one block beyond 2^40 bytes");
+    if (total > 0) {
+        HIP_TRY(c, c->rm_text.reserve((size_t)total + 64));
+        m.out = c->rm_text.as<unsigned char>();
+        m.out_cap = total;
+        hipLaunchKernelGGL(readmap_lists_write_kernel, rgrid, dim3(kDtokThreads), 0, c->stream, a, L);
         HIP_TRY(c, hipGetLastError());
     }
     ktimer_end(c, kt);

@@ -7,7 +7,8 @@ maps formatted there (csrc/wk_readmap.hpp) and the strata map joined there
 (csrc/wk_strata.hpp) -- with the hits of the coord-match, or with the reads of
 plain classification (csrc/wk_strata_reads.hpp, `_run_dstrata_reads`); read
 maps of whole-read assignments formatted there from the assignment codes
-(csrc/wk_readmap_reads.hpp, `_run_dreads_maps`).
+(csrc/wk_readmap_reads.hpp, `_run_dreads_maps`), and those with taxon lists
+(csrc/wk_readmap_lists.hpp, `_run_dreads_lists`).
 Blocks the kernels leave alone go through the host tokenizer (`_host_block`)."""
 import os
 import time
@@ -1218,7 +1219,8 @@ class DeviceTextRoute:
                                                 hdr_in, hdr, n_lines)), \
                             None, None, None, None
                     elif n_lines and self._dreadmaps is not None:
-                        yield None, ('dreads_maps', (
+                        yield None, ('dreads_lists' if self._dlists
+                                     else 'dreads_maps', (
                             text, fill, first, final, hdr_in, hdr, n_lines)), \
                             None, None, None, None
                     elif n_lines:
@@ -1850,32 +1852,56 @@ class DeviceTextRoute:
         self.tok.set_header_state(hdr)
         return n
 
-    def _sync_shown(self, namedic):
-        """The device's shown-text table (wk_readmap_reads_tables) over the
-        feature index as it is now: the ids, or their names under
-        `--name-as-id` -- set once, extended by the features `_sync_subjects`
-        has interned since."""
-        n = len(self.index)
-        have = self._shown_sent
-        if have is not None and have[0] is namedic and have[1] == n:
-            return
-        first = have[1] if have is not None and have[0] is namedic else 0
-        ids = self.index.names_of(range(first, n))
-        shown = [namedic.get(x, x) for x in ids] if namedic else ids
+    @staticmethod
+    def _text_table(texts):
+        """(bytes, offsets) of a list of strings, as the device's text tables
+        take them."""
         # (one encode for all of them: a line feed is in no id or name)
-        blob = np.frombuffer('\n'.join(shown).encode(), dtype=np.uint8)
+        blob = np.frombuffer('\n'.join(texts).encode(), dtype=np.uint8)
         cut = np.flatnonzero(blob == 10)
-        off = np.empty(n - first + 1, dtype=np.int64)
+        off = np.empty(len(texts) + 1, dtype=np.int64)
         off[0] = 0
         off[1:-1] = cut - np.arange(cut.size)
         off[-1] = blob.size - cut.size
-        if cut.size != n - first - 1:
+        if cut.size != len(texts) - 1:
             raise ValueError('a feature id or name holds a line feed')
-        self.ctx.readmap_reads_tables(first, blob[blob != 10],
-                                      off.astype(np.uint32))
-        self._shown_sent = (namedic, n)
+        return blob[blob != 10], off.astype(np.uint32)
 
-    def _run_dreads_maps(self, data, packed, sample):
+    def _sync_shown(self, namedic, ids=False):
+        """The device's shown-text table (wk_readmap_reads_tables) over the
+        feature index as it is now: the ids, or their names under
+        `--name-as-id` -- set once, extended by the features `_sync_subjects`
+        has interned since.  ``ids``: the lists of the block are ordered by
+        the ids (wk_readmap_lists_ids), which are sent next to the names when
+        the two differ."""
+        n = len(self.index)
+        have = self._shown_sent
+        if have is None or have[0] is not namedic:
+            have = (namedic, 0)
+            self._ids_sent = 0      # (a table set anew forgets the ids)
+        if have[1] < n:
+            first = have[1]
+            names = self.index.names_of(range(first, n))
+            shown = [namedic.get(x, x) for x in names] if namedic else names
+            self.ctx.readmap_reads_tables(first, *self._text_table(shown))
+            self._shown_sent = (namedic, n)
+        if ids and namedic and self._ids_sent < n:
+            first = self._ids_sent
+            self.ctx.readmap_lists_ids(first, *self._text_table(
+                self.index.names_of(range(first, n))))
+            self._ids_sent = n
+
+    def _run_dreads_lists(self, data, packed, sample):
+        """`_run_dreads_maps` for a job set in which a job can return a list
+        (`read_map_lists_on_device`): the same staging and counting; the map
+        text of every rank comes from `wk_dtok_readmap_lists`, which prints a
+        read split over several features as `taxon:count` pairs, ordered by
+        the ids the device holds next to the shown text.  Every read the
+        staging accepts is formatted there; a block it refuses goes through
+        the host tokenizer and the host formatter like there."""
+        return self._run_dreads_maps(data, packed, sample, lists=True)
+
+    def _run_dreads_maps(self, data, packed, sample, lists=False):
         """A block the device has scanned for plain classification with read
         maps of a job set in which no job returns a list: the block is staged
         as a CSR chunk of one group (`wk_dtok_stage_reads_plain`) and counted
@@ -1896,15 +1922,16 @@ class DeviceTextRoute:
         group = self._group_array(1, sample, None)
         status, n_reads, _ = self.ctx.dtok_stage_reads_plain()
         if status == 0:
-            ROUTES['dreads_maps'] += 1
+            ROUTES['dreads_lists' if lists else 'dreads_maps'] += 1
             if n_reads:
                 for rank in self.ranks:
                     data[rank].setdefault(sample, {})
-                self._sync_shown(namedic)
+                self._sync_shown(namedic, ids=lists)
                 self.ctx.set_uniform_group(group)
                 self.ctx.classify_staged_keep(self.jobs)
                 self._device_maps(sample, rank2dir, outzip, namedic,
-                                  fetch=self.ctx.dtok_readmap_reads)
+                                  fetch=self.ctx.dtok_readmap_lists if lists
+                                  else self.ctx.dtok_readmap_reads)
             self._n_reads += n_reads
             return n_reads
         n = 0

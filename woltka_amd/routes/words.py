@@ -33,6 +33,18 @@ def plain_job_ok(job):
     return job.mode in (nat.MODE_NONE, nat.MODE_RANK)
 
 
+def list_job(job):
+    """Can the job split a read over several features, so that its read map
+    holds a list?  none without --uniq, a rank without --uniq / --above /
+    --major (classify.py:32-51, 81-127)."""
+    if job.flags & nat.F_UNIQ:
+        return False
+    if job.mode == nat.MODE_NONE:
+        return True
+    return job.mode == nat.MODE_RANK and not job.flags & nat.F_ABOVE and \
+        job.major <= 0
+
+
 class WordsRoute:
     """(mixin of classify.Engine)"""
 
@@ -146,6 +158,35 @@ class WordsRoute:
                                            job.major > 0)):
                 return False
         return True
+
+    def read_map_lists_on_device(self, fmt, demux=False, strata=False,
+                                 coords=False, outcov=False, part=None,
+                                 own_text=True):
+        """Can the read maps of this file be formatted on the device when a
+        job of the set can return a list (csrc/wk_readmap_lists.hpp,
+        `_run_dreads_lists`)?  Asked where neither `device_maps_eligible` nor
+        `read_maps_on_device` took the file.  The scope of
+        `read_maps_on_device` -- plain classification with `--outmap` of a
+        whole file of SAM, BLAST tabular, PAF or simple-map text read block by
+        block, with or without `--trim-sub` / `--exclude`; not under
+        ``demux``, ``strata``, ``coords``, ``outcov`` or `--sizes`, not during
+        the replay pass, 1 to `MAX_JOBS` jobs, none size-normalised -- for the
+        sets that hold at least one job able to split a read: none without
+        --uniq, or a plain rank without --uniq / --above / --major
+        (`list_job`).  The other jobs of the set may be of any kind.
+        ``WOLTKA_NO_DLISTMAPS=1`` (like ``WOLTKA_NO_DTOK=1``) keeps the
+        general route."""
+        if os.environ.get('WOLTKA_NO_DLISTMAPS') or \
+                os.environ.get('WOLTKA_NO_DTOK'):
+            return False
+        if demux or strata or coords or outcov or self.sizes or \
+                self._replay is not None or part is not None or \
+                not own_text or fmt not in ('sam', 'b6o', 'paf', 'map') or \
+                not 1 <= len(self.jobs) <= nat.MAX_JOBS:
+            return False
+        if any(job.flags & nat.F_SIZED for job in self.jobs):
+            return False
+        return any(map(list_job, self.jobs))
 
     def _run_words(self, data, packed, sample):
         """One chunk of packed records (``('words', array, n_reads, slot)``

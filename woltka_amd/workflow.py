@@ -535,6 +535,30 @@ def classify(
                                         is None or
                                         isinstance(stream, GunzipStream))):
                                 dreadmaps = (rank2dir, outzip, namedic)
+                        # ... and of the sets in between, in which a job can
+                        # return a list: plain jobs under `--trim-sub` /
+                        # `--exclude`, list jobs next to whole-read jobs
+                        # (csrc/wk_readmap_lists.hpp)
+                        # (`dmaps` under `--exclude` is a route no block
+                        # takes -- `native_chunks` -- so it does not stand in
+                        # the way: the file is asked about as one without it)
+                        dlistmaps = None
+                        if rank2dir is not None and \
+                                (dmaps is None or exclude) and \
+                                dreadmaps is None and not want_strings:
+                            from .file import ZIP_BY_EXT, GunzipStream
+                            from os.path import splitext
+                            if engine.read_map_lists_on_device(
+                                    fmt_, demux=bool(demux),
+                                    strata=bool(stratmap),
+                                    coords=bool(ordinal),
+                                    outcov=cover is not None, part=part,
+                                    own_text=path != '-' and (
+                                        ZIP_BY_EXT.get(splitext(path)[1])
+                                        is None or
+                                        isinstance(stream, GunzipStream))):
+                                dlistmaps = (rank2dir, outzip, namedic)
+                                dmaps = None
                         chunks = engine.native_chunks(
                             stream, head, exclude, NATIVE_BLOCK, ordinal,
                             want_names, trimsub, want_groups=native_strata,
@@ -556,7 +580,8 @@ def classify(
                                 exclude=bool(exclude),
                                 n_jobs=len(engine.jobs),
                                 replay=engine._replay is not None) else None,
-                            dreads=dreads, dreadmaps=dreadmaps)
+                            dreads=dreads, dreadmaps=dreadmaps,
+                            dlistmaps=dlistmaps)
                         if ordinal and rank2dir is not None:
                             chunks = engine.regroup_hits(chunks, n)
                     else:
