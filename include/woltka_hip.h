@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define WK_ABI_VERSION 5
+#define WK_ABI_VERSION 6
 
 /* error codes */
 #define WK_OK 0
@@ -694,6 +694,53 @@ int wk_dtok_readmap_reads(wk_ctx* ctx, int32_t job, int64_t* n_bytes);
 int wk_dtok_readmap_lists(wk_ctx* ctx, int32_t job, int64_t* n_bytes);
 int wk_readmap_lists_ids(wk_ctx* ctx, int32_t first, int32_t n,
                          const uint32_t* id_off, const char* ids);
+
+/* Read maps under demultiplexing on the device (csrc/wk_readmap_demux.hpp):
+ * `--outmap` of a file that is demultiplexed (`--demux`, or a single-file
+ * input).  workflow.demultiplex (workflow.py:886-907) cuts a read id at its
+ * first '_' into (sample, read); a sample's map file holds its reads in file
+ * order, each line headed by the read part of the id.
+ *   wk_dtok_stage_reads_samples  wk_dtok_stage_reads with the sample id of
+ *                      every read kept next to its group (-1: a read the
+ *                      whitelist drops), the reads' leader lines kept as
+ *                      wk_dtok_stage_reads_plain keeps them, and the samples of
+ *                      the block given their columns.  *status = 4: the block's
+ *                      tiles (of WK_READMAP_DEMUX_TILE reads) x samples exceed
+ *                      the partition's matrix (option "readmap_demux_cap",
+ *                      entries; 0: 2^23): no chunk is left staged and nothing
+ *                      has been counted (the samples' "met" bytes of the
+ *                      refused block may be set on the device; the next
+ *                      staging clears them and wk_demux_fetch refuses until
+ *                      then); the host tokenizer takes the block, as for
+ *                      every other status != 0.
+ *   wk_dtok_readmap_reads_demux / wk_dtok_readmap_lists_demux
+ *                      wk_dtok_readmap_reads / wk_dtok_readmap_lists over that
+ *                      chunk, behind wk_classify_staged_keep: the text of job j
+ *                      as one run per sample of the block, samples ascending by
+ *                      id, every run in read order; a read the whitelist drops
+ *                      has no line.  *n_bytes = its size (wk_dtok_readmap_fetch
+ *                      copies it out), *n_segments = the runs, one per sample
+ *                      that has a read in the block (its run may be empty).
+ *   wk_dtok_readmap_segments  (sample id, first byte, bytes) of every run of
+ *                      the text made last: seg[3 * k ...], cap >= *n_segments.
+ *   wk_readmap_demux_partition  (tests) the partition alone: samp[n] (-1: no
+ *                      line) and len[n] (0: no line) -> off[r] = the sum of
+ *                      len over all (samp', r') < (samp, r); the segments
+ *                      (seg_cap >= the samples present), *n_seg, *total.
+ *                      *status = 1: tiles x samples beyond the capacity,
+ *                      nothing is written. */
+#define WK_READMAP_DEMUX_TILE 512
+int wk_dtok_stage_reads_samples(wk_ctx* ctx, int64_t* n_reads,
+                                int64_t* n_records, int* status);
+int wk_dtok_readmap_reads_demux(wk_ctx* ctx, int32_t job, int64_t* n_bytes,
+                                int32_t* n_segments);
+int wk_dtok_readmap_lists_demux(wk_ctx* ctx, int32_t job, int64_t* n_bytes,
+                                int32_t* n_segments);
+int wk_dtok_readmap_segments(wk_ctx* ctx, uint64_t* seg, int32_t cap);
+int wk_readmap_demux_partition(wk_ctx* ctx, const int32_t* samp,
+                               const uint64_t* len, int64_t n, uint64_t* off,
+                               uint64_t* seg, int32_t seg_cap, int32_t* n_seg,
+                               uint64_t* total, int* status);
 
 /* Convenience: stage + classify in one call from host buffers. */
 int wk_classify_chunk(wk_ctx* ctx, const wk_job* jobs, int32_t n_jobs,

@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get('WOLTKA_HIP_LIB') or os.path.join(
     _HERE, 'libwoltka_hip.so')
 
 # constants mirrored from include/woltka_hip.h
-ABI_VERSION = 5
+ABI_VERSION = 6
 OK, E_HIP, E_ARG, E_STATE, E_CAPACITY, E_RANGE, E_TABLE_FULL = (
     0, -1, -2, -3, -4, -5, -6)
 KEY_FEATURE_BITS, KEY_GROUP_BITS, KEY_K_BITS, KEY_JOB_BITS = 28, 21, 12, 3
@@ -27,6 +27,7 @@ F_UNIQ, F_ABOVE, F_SUBOK, F_UNASSIGNED, F_SIZED = 1, 2, 4, 8, 16
 ASSIGN_NONE, ASSIGN_MULTI, ASSIGN_EMPTY = -1, -2, -3
 SUBJ_IS_SET, SUBJ_INDEXED, GROUP_UNIFORM = 1, 2, 4
 MAX_RANK_SLOTS = MAX_JOBS * 4
+READMAP_DEMUX_TILE = 512
 
 # every symbol the header declares (checked by tests/test_abi.py)
 SYMBOLS = (
@@ -69,6 +70,9 @@ SYMBOLS = (
     'wk_dtok_stage_reads_plain', 'wk_classify_staged_keep',
     'wk_readmap_reads_tables', 'wk_dtok_readmap_reads',
     'wk_dtok_readmap_lists', 'wk_readmap_lists_ids',
+    'wk_dtok_stage_reads_samples', 'wk_dtok_readmap_reads_demux',
+    'wk_dtok_readmap_lists_demux', 'wk_dtok_readmap_segments',
+    'wk_readmap_demux_partition',
     'wk_tok_subjects',
     'wk_tok_new_subjects', 'wk_tok_fetch_groups', 'wk_tok_strata_clear',
     'wk_tok_strata_load', 'wk_tok_strata_labels', 'wk_tok_strata_select',
@@ -287,6 +291,19 @@ def load_library():
                                               C.c_void_p]),
         'wk_dtok_readmap_reads': (C.c_int, [p, C.c_int32, i64p]),
         'wk_dtok_readmap_lists': (C.c_int, [p, C.c_int32, i64p]),
+        'wk_dtok_stage_reads_samples': (C.c_int, [p, i64p, i64p,
+                                                  C.POINTER(C.c_int)]),
+        'wk_dtok_readmap_reads_demux': (C.c_int, [p, C.c_int32, i64p,
+                                                  C.POINTER(C.c_int32)]),
+        'wk_dtok_readmap_lists_demux': (C.c_int, [p, C.c_int32, i64p,
+                                                  C.POINTER(C.c_int32)]),
+        'wk_dtok_readmap_segments': (C.c_int, [p, C.POINTER(C.c_uint64),
+                                               C.c_int32]),
+        'wk_readmap_demux_partition': (C.c_int, [
+            p, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.c_int64,
+            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int32,
+            C.POINTER(C.c_int32), C.POINTER(C.c_uint64),
+            C.POINTER(C.c_int)]),
         'wk_readmap_lists_ids': (C.c_int, [p, C.c_int32, C.c_int32, u32p,
                                            C.c_void_p]),
         'wk_tok_subjects': (C.c_int, [p, i32p, i32p, i64p]),
@@ -1233,6 +1250,64 @@ class Context:
             self._check(self._lib.wk_dtok_readmap_fetch(
                 self._h, C.c_void_p(out.ctypes.data), out.size))
         return out[:n.value], inside
+
+    # -- read maps under demultiplexing (csrc/wk_readmap_demux.hpp) --
+    def dtok_stage_reads_samples(self):
+        """``dtok_stage_reads`` with the sample id of every read and the
+        reads' leader lines kept for ``dtok_readmap_demux``.  Returns (status,
+        reads, records); status != 0: the host tokenizer takes the block (4:
+        more tiles x samples than option ``readmap_demux_cap`` allows)."""
+        a, b, st = C.c_int64(0), C.c_int64(0), C.c_int(1)
+        self._check(self._lib.wk_dtok_stage_reads_samples(
+            self._h, C.byref(a), C.byref(b), C.byref(st)))
+        if st.value == 0:
+            self._n_reads = a.value
+        return st.value, a.value, b.value
+
+    def dtok_readmap_demux(self, job, lists=False, out=None):
+        """Read-map text of the chunk ``dtok_stage_reads_samples`` staged last
+        at job ``job``, from the codes ``classify_staged_keep`` left, cut into
+        one run per sample: (uint8 array, whether it lies in ``out``,
+        uint64[n, 3] of (sample id, first byte, bytes) ascending by id).
+        ``lists``: by the list formatter (any kind of job)."""
+        n, k = C.c_int64(0), C.c_int32(0)
+        fn = self._lib.wk_dtok_readmap_lists_demux if lists \
+            else self._lib.wk_dtok_readmap_reads_demux
+        self._check(fn(self._h, int(job), C.byref(n), C.byref(k)))
+        seg = np.zeros((k.value, 3), dtype=np.uint64)
+        if k.value:
+            self._check(self._lib.wk_dtok_readmap_segments(
+                self._h, _ptr(seg, C.c_uint64), k.value))
+        inside = out is not None and out.size >= n.value
+        if not inside:
+            out = np.empty(n.value, dtype=np.uint8)
+        if n.value:
+            self._check(self._lib.wk_dtok_readmap_fetch(
+                self._h, C.c_void_p(out.ctypes.data), out.size))
+        return out[:n.value], inside, seg
+
+    def readmap_demux_partition(self, samp, length):
+        """(tests) the partition of ``dtok_readmap_demux`` alone: sample ids
+        (int32, -1: no line) and line lengths (uint64) -> (status, off
+        uint64[n], segments uint64[D, 3], total).  status 1: tiles x samples
+        beyond option ``readmap_demux_cap``; the outputs are None then."""
+        samp = _arr(samp, np.int32)
+        length = _arr(length, np.uint64)
+        if samp.size != length.size:
+            raise ValueError('one length per read')
+        off = np.zeros(samp.size, dtype=np.uint64)
+        cap = 1 << 16
+        seg = np.zeros((cap, 3), dtype=np.uint64)
+        k, total, st = C.c_int32(0), C.c_uint64(0), C.c_int(1)
+        self._check(self._lib.wk_readmap_demux_partition(
+            self._h, _ptr(samp, C.c_int32) if samp.size else None,
+            _ptr(length, C.c_uint64) if samp.size else None, samp.size,
+            _ptr(off, C.c_uint64) if samp.size else None,
+            _ptr(seg, C.c_uint64), cap, C.byref(k), C.byref(total),
+            C.byref(st)))
+        if st.value:
+            return st.value, None, None, None
+        return 0, off, seg[:k.value].copy(), total.value
 
     def ordinal_hit_offsets(self, n_hits):
         """Offsets of every hit's genes in the staged gene lists

@@ -252,6 +252,8 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
         self._dx_names = None       # the device's sample table: slot -> name (None: not begun)
         self._dx_key = None         # (epoch, samples) the device holds groups for
         self._dx_full = False       # the table refused a block of this file: the rest on the host
+        # ... with read maps, cut into one run per sample on the device (csrc/wk_readmap_demux.hpp)
+        self._ddemuxmaps = None     # (whitelist or None, rank2dir, outzip, namedic) while a file is read that way
         self._cv_cover, self._cv_sample = None, None    # whose ranges the device's coverage pile holds
         self._cv_open = False
         self._ring, self._ring_prev = None, None    # packed-record staging
@@ -440,7 +442,7 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
                       fmt='sam', part=None, words=False, dmaps=None,
                       keep_empty=False, words_dev=False, dcover=False,
                       ddemux=None, dreads=False, dhdemux=None,
-                      dreadmaps=None, dlistmaps=None):
+                      dreadmaps=None, dlistmaps=None, ddemuxmaps=None):
         """SAM text -> packed chunks through the native tokenizer.  Yields
         (reads or None, packed, strata ids, name descriptors, sample ids,
         ranges) where packed = (subj, qoff) of subject indices, or for
@@ -468,7 +470,12 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
         ``dlistmaps`` (`read_map_lists_on_device`): the same triple for a set
         in which a job can return a list, asked when neither ``dmaps`` nor
         ``dreadmaps`` took the file: the same blocks, the maps formatted by
-        the list formatter (`_run_dreads_lists`)."""
+        the list formatter (`_run_dreads_lists`).  ``ddemuxmaps``
+        (`demux_read_maps_on_device`): (whitelist or None, rank2dir, outzip,
+        namedic) -- plain classification with read maps of a file that is
+        demultiplexed: the samples are told on the device, the blocks counted
+        as CSR chunks with a group per read and the maps formatted there, one
+        run of text per sample (`_run_dreads_demux`)."""
         from .align import native_sam_blocks
         if self.tok is None:
             # (a tokenizer whose dictionary was filled from this file's first
@@ -507,6 +514,14 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
             not ordinal and cover is None and not want_groups and
             not want_samples and part is None and
             len(self.jobs) <= nat.MAX_JOBS) else None
+        ddemuxmaps = ddemuxmaps if (
+            ddemuxmaps is not None and ddemux is None and dreadmaps is None
+            and not (words or words_dev or dmaps or ordinal or want_groups or
+                     want_samples or dreads or dcover) and cover is None and
+            part is None and len(self.jobs) <= nat.MAX_JOBS) else None
+        if ddemuxmaps is not None:
+            # (the samples are looked up and registered as for `_run_ddemux`)
+            ddemux, dlistmaps = (ddemuxmaps[0],), None
         dlists = False
         if dreadmaps is None and dlistmaps is not None and not (
                 words or words_dev or dmaps or ordinal or want_groups or
@@ -547,6 +562,7 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
                     else None
                 self._dcover = cover if dcover else None
                 self._ddemux = ddemux
+                self._ddemuxmaps = ddemuxmaps
                 self._dreads = dreads
                 self._dreadmaps = dreadmaps
                 self._dlists = dlists
@@ -589,6 +605,7 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
                     self._dmaps = None
                     self._dcover = None
                     self._ddemux = None
+                    self._ddemuxmaps = None
                     self._dhdemux = None
                     self._dreads = False
                     self._dreadmaps = None
@@ -830,6 +847,7 @@ class Engine(DeviceTextRoute, WordsRoute, CoordMatchRoute, ReadMaps, Replay,
                 'dreads': '_run_dstrata_reads',     # ... -> CSR chunk with the reads' strata joined on the device, counted likewise
                 'dreads_maps': '_run_dreads_maps',  # ... -> CSR chunk of one group, counted likewise, read maps formatted from the codes on the device
                 'dreads_lists': '_run_dreads_lists',    # ... the same for a set with a job that returns lists
+                'dreads_demux': '_run_dreads_demux',    # ... -> demultiplexed CSR chunk, read maps formatted on the device and cut per sample
                 'words': '_run_words'}      # packed records of the host tokenizer (routes/words.py)
 
     def _run_general(self, data, reads, subque, sample_of, strata_of, trimsub,

@@ -227,7 +227,9 @@ __global__ void __launch_bounds__(kDtokThreads) demux_pending_kernel(DtokArgs a,
 // lower mates in the run + its position in its read (dtok_place_words_kernel); a read's index likewise from its first
 // record, which also looks the read's sample up: its group, and -- unless the whitelist drops it -- the sample's
 // "met" byte (a plain store: every writer stores 1).
-__global__ void __launch_bounds__(kDtokThreads) demux_place_reads_kernel(DtokArgs a, DemuxArgs d) {
+// `rsamp` (optional): the sample id of every read next to its group, -1 for a read the whitelist drops or whose
+// sample the table does not hold (the read maps under demultiplexing cut their text by it, wk_readmap_demux.hpp).
+__global__ void __launch_bounds__(kDtokThreads) demux_place_reads_kernel(DtokArgs a, DemuxArgs d, int32_t* __restrict__ rsamp) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.n_lines || !(a.is_first[i] & 1u)) return;
     const uint32_t m = a.lmeta[i] >> 28;
@@ -271,6 +273,7 @@ __global__ void __launch_bounds__(kDtokThreads) demux_place_reads_kernel(DtokArg
         if (r < d.cap) {
             d.c_qoff[r] = (int32_t)at;
             d.c_group[r] = g;
+            if (rsamp) rsamp[r] = g >= 0 ? id : -1;
         }
     }
 }

@@ -83,6 +83,7 @@ __device__ __forceinline__ uint32_t lists_piece_len(const ReadmapListsArgs& L, u
 }
 
 // The line of list r with `pieces` bytes of pairs (lane 0 / thread 0 of the read's team)
+template <bool kDemux = false>
 __device__ __forceinline__ void lists_set_len(const DtokArgs& a, const ReadmapListsArgs& L, uint32_t r, uint32_t n_pairs,
                                               unsigned long long pieces) {
     const uint32_t i = L.m.read_line[r];
@@ -90,8 +91,8 @@ __device__ __forceinline__ void lists_set_len(const DtokArgs& a, const ReadmapLi
     if (n_pairs == 0) {
         atomicOr(L.m.flags, kReadsBadCode);  // (a list holds two values that differ: one of them is a feature)
     } else if (i < a.n_lines) {
-        const uint32_t meta = a.lmeta[i];
-        len = (unsigned long long)(meta & 0x0FFFFFFFu) + ((meta >> 28) ? 2u : 0u) + pieces + 1u;
+        const ReadmapId id = readmap_id<kDemux>(a, i);
+        len = (unsigned long long)id.n + (id.mate ? 2u : 0u) + pieces + 1u;
     } else {
         n_pairs = 0;  // (a read no leader names has no line, as with a single code)
     }
@@ -100,6 +101,7 @@ __device__ __forceinline__ void lists_set_len(const DtokArgs& a, const ReadmapLi
 }
 
 // A wave builds the list of read r: n <= 64 subjects from record lo on, one per lane.
+template <bool kDemux = false>
 __device__ __forceinline__ void lists_wave_build(const DtokArgs& a, const ReadmapListsArgs& L, uint32_t r, int32_t lo, int32_t n,
                                                  uint32_t lane) {
     const bool mine = (int32_t)lane < n;
@@ -129,7 +131,7 @@ __device__ __forceinline__ void lists_wave_build(const DtokArgs& a, const Readma
     }
     if (head) L.pairs[lo + place] = make_uint2((uint32_t)t, count);
     const unsigned long long pieces = wave_sum(head ? (unsigned long long)lists_piece_len(L, (uint32_t)t, count) : 0ull);
-    if (lane == 0) lists_set_len(a, L, r, (uint32_t)__popcll(heads), pieces);
+    if (lane == 0) lists_set_len<kDemux>(a, L, r, (uint32_t)__popcll(heads), pieces);
 }
 
 // Bitonic sort of key[0, m2), m2 a power of two, by the whole workgroup (which has met at a barrier).
@@ -152,6 +154,7 @@ __device__ __forceinline__ void lists_bitonic(unsigned long long* key, uint32_t 
 }
 
 // The workgroup builds the list of read r: 64 < n <= WK_MAX_K subjects from record lo on.
+template <bool kDemux = false>
 __device__ __forceinline__ void lists_block_build(const DtokArgs& a, const ReadmapListsArgs& L, uint32_t r, int32_t lo, int32_t n,
                                                   unsigned long long* key, uint32_t* aux, unsigned long long* red) {
     const uint32_t tid = threadIdx.x;
@@ -213,12 +216,15 @@ __device__ __forceinline__ void lists_block_build(const DtokArgs& a, const Readm
     if (tid == 0) {
         unsigned long long all = 0;
         for (uint32_t w = 0; w < kDtokThreads / kWave; ++w) all += red[w];
-        lists_set_len(a, L, r, (uint32_t)(all >> 40), all & ((1ull << 40) - 1ull));
+        lists_set_len<kDemux>(a, L, r, (uint32_t)(all >> 40), all & ((1ull << 40) - 1ull));
     }
     __syncthreads();
 }
 
-__global__ void __launch_bounds__(kDtokThreads) readmap_lists_build_kernel(DtokArgs a, ReadmapListsArgs L) {
+// The tile of blockIdx.x.  kDemux: the read part of the id is printed, and a read whose sample the whitelist drops
+// (samp[r] < 0) has no line (wk_readmap_demux.hpp).
+template <bool kDemux>
+__device__ __forceinline__ void lists_build_tile(const DtokArgs& a, const ReadmapListsArgs& L, const int32_t* __restrict__ samp) {
     __shared__ unsigned long long key[kListsLds];
     __shared__ uint32_t aux[kListsLds];
     __shared__ unsigned long long red[kDtokThreads / kWave];
@@ -232,8 +238,11 @@ __global__ void __launch_bounds__(kDtokThreads) readmap_lists_build_kernel(DtokA
     bool list = false;
     if (r < L.m.n_reads) {
         const int32_t v = L.m.assign[r];
-        if (v != WK_ASSIGN_MULTI) {
-            L.m.read_len[r] = readmap_reads_line_len(a, L.m, r, v);
+        if (kDemux && samp[r] < 0) {
+            L.n_pairs[r] = 0;
+            L.m.read_len[r] = 0;
+        } else if (v != WK_ASSIGN_MULTI) {
+            L.m.read_len[r] = readmap_reads_line_len<kDemux>(a, L.m, r, v);
         } else {
             lo = L.qoff[r];
             n = L.qoff[r + 1] - lo;
@@ -249,27 +258,33 @@ __global__ void __launch_bounds__(kDtokThreads) readmap_lists_build_kernel(DtokA
     if (large) big[atomicAdd(&n_big, 1u)] = tid;
     for (unsigned long long todo = __ballot(list && !large); todo; todo &= todo - 1ull) {
         const int src = __ffsll((long long)todo) - 1;
-        lists_wave_build(a, L, r - lane + (uint32_t)src, __shfl(lo, src, kWave), __shfl(n, src, kWave), lane);
+        lists_wave_build<kDemux>(a, L, r - lane + (uint32_t)src, __shfl(lo, src, kWave), __shfl(n, src, kWave), lane);
     }
     __syncthreads();
     const uint32_t todo_big = n_big;
     for (uint32_t b = 0; b < todo_big; ++b) {
         const uint32_t rb = blockIdx.x * kDtokThreads + big[b];
         const int32_t lb = L.qoff[rb];
-        lists_block_build(a, L, rb, lb, L.qoff[rb + 1] - lb, key, aux, red);
+        lists_block_build<kDemux>(a, L, rb, lb, L.qoff[rb + 1] - lb, key, aux, red);
     }
 }
 
-// A wave writes the line of list r at read_len[r] (now the exclusive prefix).
+__global__ void __launch_bounds__(kDtokThreads) readmap_lists_build_kernel(DtokArgs a, ReadmapListsArgs L) {
+    lists_build_tile<false>(a, L, nullptr);
+}
+
+// A wave writes the line of list r at read_len[r] (now the exclusive prefix, or the place the partition gave it).
+template <bool kDemux = false>
 __device__ __forceinline__ void lists_wave_write(const DtokArgs& a, const ReadmapListsArgs& L, uint32_t r, uint32_t lane) {
     const uint32_t n_pairs = L.n_pairs[r];
     const uint32_t i = L.m.read_line[r];
     if (n_pairs == 0 || i >= a.n_lines) return;
     unsigned long long at = L.m.read_len[r];
     const unsigned long long cap = L.m.out_cap;
-    const uint32_t qn = a.lmeta[i] & 0x0FFFFFFFu, mate = a.lmeta[i] >> 28;
+    const ReadmapId id = readmap_id<kDemux>(a, i);
+    const uint32_t qn = id.n, mate = id.mate ? a.lmeta[i] >> 28 : 0u;
     unsigned char* o = L.m.out;
-    const unsigned char* q = a.text + a.line_start[i];
+    const unsigned char* q = a.text + id.off;
     for (uint32_t k = lane; k < qn; k += kWave)
         if (at + k < cap) o[at + k] = q[k];
     at += qn;
@@ -313,17 +328,23 @@ __device__ __forceinline__ void lists_wave_write(const DtokArgs& a, const Readma
     if (lane == 0 && at < cap) o[at] = '\n';
 }
 
-__global__ void __launch_bounds__(kDtokThreads) readmap_lists_write_kernel(DtokArgs a, ReadmapListsArgs L) {
+template <bool kDemux>
+__device__ __forceinline__ void lists_write_tile(const DtokArgs& a, const ReadmapListsArgs& L, const int32_t* __restrict__ samp) {
     const uint32_t r = blockIdx.x * kDtokThreads + threadIdx.x;
     const uint32_t lane = threadIdx.x & (kWave - 1);
     bool list = false;
     if (r < L.m.n_reads) {
         const int32_t v = L.m.assign[r];
-        list = v == WK_ASSIGN_MULTI;
-        if (!list) readmap_reads_write_line(a, L.m, r, v);
+        const bool drop = kDemux && samp[r] < 0;
+        list = v == WK_ASSIGN_MULTI && !drop;
+        if (!list && !drop) readmap_reads_write_line<kDemux>(a, L.m, r, v);
     }
     for (unsigned long long todo = __ballot(list); todo; todo &= todo - 1ull)
-        lists_wave_write(a, L, r - lane + (uint32_t)(__ffsll((long long)todo) - 1), lane);
+        lists_wave_write<kDemux>(a, L, r - lane + (uint32_t)(__ffsll((long long)todo) - 1), lane);
+}
+
+__global__ void __launch_bounds__(kDtokThreads) readmap_lists_write_kernel(DtokArgs a, ReadmapListsArgs L) {
+    lists_write_tile<false>(a, L, nullptr);
 }
 
 }  // namespace wk

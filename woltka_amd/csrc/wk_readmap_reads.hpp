@@ -48,6 +48,30 @@ __global__ void __launch_bounds__(kDtokThreads) readmap_leaders_kernel(DtokArgs 
     if (r < n_reads) read_line[r] = i;
 }
 
+// The bytes of the id of the read led by line i that a map line prints in front of the mate suffix: (offset in
+// the text, length).  kDemux: the read part of the id as workflow.demultiplex leaves it (wk_readmap_demux.hpp).
+struct ReadmapId {
+    uint32_t off, n;
+    bool mate;  // "/1" | "/2" follows
+};
+
+template <bool kDemux>
+__device__ __forceinline__ ReadmapId readmap_id(const DtokArgs& a, uint32_t i) {
+    const uint32_t lo = a.line_start[i], meta = a.lmeta[i];
+    const uint32_t qn = meta & 0x0FFFFFFFu;
+    const bool mate = (meta >> 28) != 0u;
+    if (!kDemux) return ReadmapId{lo, qn, mate};
+    uint32_t u = qn;
+    for (uint32_t k = 0; k < qn; ++k)
+        if (a.text[lo + k] == '_') {
+            u = k;
+            break;
+        }
+    if (u == qn) return ReadmapId{lo, qn, mate};                    // no '_': the whole id
+    if (u + 1u == qn && !mate) return ReadmapId{lo, qn - 1u, false};  // "S1_" unpaired: right is empty, the read is left
+    return ReadmapId{lo + u + 1u, qn - u - 1u, mate};                 // everything behind the first '_'
+}
+
 // Bytes shown for code v: 0 = no line.  A code that cannot be printed raises the flag.
 __device__ __forceinline__ uint32_t readmap_reads_shown(const ReadmapReadsArgs& m, int32_t v) {
     if (v >= 0) {
@@ -63,6 +87,7 @@ __device__ __forceinline__ uint32_t readmap_reads_shown(const ReadmapReadsArgs& 
 }
 
 // The length of read r's line under code v (0: none)
+template <bool kDemux = false>
 __device__ __forceinline__ unsigned long long readmap_reads_line_len(const DtokArgs& a, const ReadmapReadsArgs& m, uint32_t r, int32_t v) {
     const uint32_t i = m.read_line[r];
     unsigned long long len = 0;
@@ -70,8 +95,8 @@ __device__ __forceinline__ unsigned long long readmap_reads_line_len(const DtokA
     const uint32_t shown = readmap_reads_shown(m, v);
     const bool line = i < a.n_lines && ((v >= 0 && (uint32_t)v < m.n_shown) || (v == WK_ASSIGN_NONE && m.unassigned));
     if (line) {
-        const uint32_t meta = a.lmeta[i];
-        len = (unsigned long long)(meta & 0x0FFFFFFFu) + ((meta >> 28) ? 2u : 0u) + 1u + shown + 1u;
+        const ReadmapId id = readmap_id<kDemux>(a, i);
+        len = (unsigned long long)id.n + (id.mate ? 2u : 0u) + 1u + shown + 1u;
     }
     return len;
 }
@@ -83,7 +108,8 @@ __global__ void __launch_bounds__(kDtokThreads) readmap_reads_len_kernel(DtokArg
     m.read_len[r] = readmap_reads_line_len(a, m, r, m.assign[r]);
 }
 
-// Read r's line under code v at read_len[r] (now the exclusive prefix)
+// Read r's line under code v at read_len[r] (now the exclusive prefix, or the place the partition gave it)
+template <bool kDemux = false>
 __device__ __forceinline__ void readmap_reads_write_line(const DtokArgs& a, const ReadmapReadsArgs& m, uint32_t r, int32_t v) {
     const uint32_t i = m.read_line[r];
     if (i >= a.n_lines) return;
@@ -99,10 +125,11 @@ __device__ __forceinline__ void readmap_reads_write_line(const DtokArgs& a, cons
         return;
     }
     unsigned long long at = m.read_len[r];
-    const uint32_t qn = a.lmeta[i] & 0x0FFFFFFFu, mate = a.lmeta[i] >> 28;
+    const ReadmapId id = readmap_id<kDemux>(a, i);
+    const uint32_t qn = id.n, mate = id.mate ? a.lmeta[i] >> 28 : 0u;
     if (at + qn + (mate ? 2u : 0u) + 2u + n > m.out_cap) return;  // (the lengths said otherwise: nothing past the text)
     unsigned char* o = m.out;
-    const unsigned char* q = a.text + a.line_start[i];
+    const unsigned char* q = a.text + id.off;
     for (uint32_t k = 0; k < qn; ++k) o[at + k] = q[k];
     at += qn;
     if (mate) {

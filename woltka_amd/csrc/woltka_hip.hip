@@ -32,6 +32,7 @@
 #include "wk_readmap.hpp"
 #include "wk_readmap_reads.hpp"
 #include "wk_readmap_lists.hpp"
+#include "wk_readmap_demux.hpp"
 #include "wk_tok_internal.h"
 #include "wk_weigh.hpp"
 #include "wk_weigh_wide.hpp"
@@ -476,6 +477,13 @@ struct wk_ctx {
     uint32_t rl_text_n = 0;
     int32_t rl_mode[WK_MAX_JOBS] = {};
     int32_t rl_slot[WK_MAX_JOBS] = {};
+    // read maps under demultiplexing (wk_readmap_demux.hpp): the sample id of every read of the staged chunk, the
+    // samples' columns, the partition's matrix, column bases, segment table and the lines' places
+    DevBuf rd_samp, pd_present, pd_state, pd_mat, pd_col, pd_seg, pd_off;
+    bool rd_chunk = false;        // the staged chunk is wk_dtok_stage_reads_samples': rd_samp, rm_line and the columns are its reads'
+    uint32_t rd_cols = 0;         // ... and the samples it holds
+    int32_t rd_segs = 0;          // segments of the text wk_dtok_readmap_*_demux made last
+    int64_t pd_cap_opt = 0;       // option "readmap_demux_cap": entries of the matrix (0: kPartCapDefault)
     int range_parts_opt = 0;   // partitions of the dense gene log (0: as few as the merge's LDS array allows; measurement)
     int use_streams = 1;   // (0: the records of all slices in one stream, round 3's team kernel; measurement)
     int use_subject_bins = 1;
@@ -1184,7 +1192,8 @@ void wk_destroy(wk_ctx* c) {
                       &c->cv_reach, &c->cv_hist, &c->cv_tiles, &c->cv_tile_off, &c->cv_state, &c->cv_stage[0], &c->cv_stage[1], &c->cv_stage[2],
                       &c->dx_tab, &c->dx_name_off, &c->dx_arena, &c->dx_group, &c->dx_met, &c->dx_pend, &c->dx_pend_list, &c->dx_state, &c->dx_lsamp, &c->dx_out, &c->dx_rsamp,
                       &c->rr_off, &c->rr_text, &c->rr_flags,
-                      &c->rl_off, &c->rl_text, &c->rl_pairs, &c->rl_npairs})
+                      &c->rl_off, &c->rl_text, &c->rl_pairs, &c->rl_npairs,
+                      &c->rd_samp, &c->pd_present, &c->pd_state, &c->pd_mat, &c->pd_col, &c->pd_seg, &c->pd_off})
         b->release();
     for (wk_ctx::ResidentText& r : c->resident) {
         (void)hipFree(r.dev);
@@ -1248,6 +1257,11 @@ int wk_set_option(wk_ctx* c, const char* name, int64_t value) {
     if (!strcmp(name, "demux_max_samples")) {  // (tests) samples the table takes, 0: kDemuxMaxSamples; before wk_demux_begin
         if (value < 0 || value > (int64_t)kDemuxMaxSamples) return fail(c, WK_E_ARG, "demux_max_samples must be in [0, %u]", kDemuxMaxSamples);
         c->dx_max_opt = value;
+        return WK_OK;
+    }
+    if (!strcmp(name, "readmap_demux_cap")) {  // entries (tiles x samples of a block) of the matrix the read maps under demultiplexing are partitioned with, 0: the default; a block beyond it is the host's
+        if (value < 0 || value > kPartCapMax) return fail(c, WK_E_ARG, "readmap_demux_cap must be in [0, %lld]", (long long)kPartCapMax);
+        c->pd_cap_opt = value;
         return WK_OK;
     }
     return fail(c, WK_E_ARG, "unknown option '%s' (launch shapes and ablation switches: wk_tune)", name);
@@ -1787,6 +1801,7 @@ int wk_chunk_stage(wk_ctx* c, const int32_t* subj, const int32_t* qoff, int64_t 
     c->chunk_valid = true;
     c->dx_chunk = false;
     c->rr_chunk = false;
+    c->rd_chunk = false;
     return WK_OK;
 }
 
@@ -5107,6 +5122,7 @@ static int dtok_stage_impl(wk_ctx* c, const int32_t* genome_of_subject, int32_t 
     c->acc_open = append;
     c->dx_chunk = false;
     c->rr_chunk = false;
+    c->rd_chunk = false;
     c->dx_hits = false;
     *n_reads = reads;
     *n_hits = hits;
@@ -5148,6 +5164,7 @@ int wk_demux_begin(wk_ctx* c, int on) {
     c->dx_looked = false;
     c->dx_chunk = false;
     c->rr_chunk = false;
+    c->rd_chunk = false;
     c->dx_hits = false;
     c->dx_groups_n = 0;
     c->dx_name_off_host.clear();
@@ -5354,10 +5371,11 @@ int wk_demux_register(wk_ctx* c, const char* blob, const int64_t* off, int32_t n
     return WK_OK;
 }
 
-enum StageReads { kStageDemux = 0, kStageStrata = 1, kStagePlain = 2 };
+enum StageReads { kStageDemux = 0, kStageStrata = 1, kStagePlain = 2, kStageDemuxKeep = 3 };
 static int stage_reads_chunk(wk_ctx* c, StageReads how, int64_t* n_reads, int64_t* n_records, int* status);
 
-int wk_dtok_stage_reads(wk_ctx* c, int64_t* n_reads, int64_t* n_records, int* status) {
+// wk_dtok_stage_reads / wk_dtok_stage_reads_samples: the checks, the lookup of the samples if it has not run, the chunk
+static int stage_reads_demux(wk_ctx* c, StageReads how, int64_t* n_reads, int64_t* n_records, int* status) {
     if (!c || !n_reads || !n_records || !status) return WK_E_ARG;
     *status = 1;
     *n_reads = *n_records = 0;
@@ -5379,7 +5397,11 @@ int wk_dtok_stage_reads(wk_ctx* c, int64_t* n_reads, int64_t* n_records, int* st
         }
         if (!c->dx_pend_off.empty()) return fail(c, WK_E_STATE, "the block brings samples the table does not hold (wk_demux_pending, wk_demux_register)");
     }
-    return stage_reads_chunk(c, kStageDemux, n_reads, n_records, status);
+    return stage_reads_chunk(c, how, n_reads, n_records, status);
+}
+
+int wk_dtok_stage_reads(wk_ctx* c, int64_t* n_reads, int64_t* n_records, int* status) {
+    return stage_reads_demux(c, kStageDemux, n_reads, n_records, status);
 }
 
 // The block scanned last for the plain flavour as the staged CSR chunk with a group per read: the group of the read's
@@ -5388,13 +5410,15 @@ int wk_dtok_stage_reads(wk_ctx* c, int64_t* n_reads, int64_t* n_records, int* st
 // them (wk_set_uniform_group), and the reads' leader lines are kept for wk_dtok_readmap_reads (wk_readmap_reads.hpp).
 // *status stays 1 for a block the kernels leave to the host tokenizer.
 static int stage_reads_chunk(wk_ctx* c, StageReads how, int64_t* n_reads, int64_t* n_records, int* status) {
-    const bool strata = how != kStageDemux;  // (run starts told here; no samples to look up)
+    const bool keep = how == kStageDemuxKeep;  // (the reads' sample ids and leader lines are kept: wk_readmap_demux.hpp)
+    const bool strata = how != kStageDemux && !keep;  // (run starts told here; no samples to look up)
     const bool plain = how == kStagePlain;
     c->dt_ready = false;
     c->dx_looked = false;
     c->chunk_valid = false;
     c->dx_chunk = false;
     c->rr_chunk = false;
+    c->rd_chunk = false;
     c->dx_hits = false;
     const uint32_t lines = c->dt_lines;
     const size_t n_samples = strata ? 0 : c->dx_name_off_host.size();
@@ -5405,6 +5429,7 @@ static int stage_reads_chunk(wk_ctx* c, StageReads how, int64_t* n_reads, int64_
     HIP_TRY(c, c->c_subj.reserve((size_t)lines * 4 + 64));
     HIP_TRY(c, c->c_qoff.reserve(((size_t)lines + 2) * 4));
     HIP_TRY(c, c->c_group.reserve(((size_t)lines + 1) * 4));
+    if (keep) HIP_TRY(c, c->rd_samp.reserve(((size_t)lines + 1) * 4));
     if (lines > 0) {
         DtokArgs a = dtok_args(c);
         const uint32_t n_tiles = (lines + kDtokThreads - 1) / kDtokThreads;
@@ -5437,7 +5462,7 @@ static int stage_reads_chunk(wk_ctx* c, StageReads how, int64_t* n_reads, int64_
             d.c_qoff = c->c_qoff.as<int32_t>();
             d.c_group = c->c_group.as<int32_t>();
             d.cap = lines;
-            hipLaunchKernelGGL(demux_place_reads_kernel, grid, dim3(kDtokThreads), 0, c->stream, a, d);
+            hipLaunchKernelGGL(demux_place_reads_kernel, grid, dim3(kDtokThreads), 0, c->stream, a, d, keep ? c->rd_samp.as<int32_t>() : nullptr);
         }
         ktimer_end(c, kt);
         HIP_TRY(c, hipGetLastError());
@@ -5460,7 +5485,7 @@ static int stage_reads_chunk(wk_ctx* c, StageReads how, int64_t* n_reads, int64_
     c->stage_serial += 1;
     c->cur_subj = c->c_subj.as<int32_t>();
     c->cur_qoff = c->c_qoff.as<int32_t>();
-    if (plain && reads > 0) {
+    if ((plain || keep) && reads > 0) {
         // the leader line of every read, in the chunk's read order (a read no leader names keeps "no line")
         HIP_TRY(c, c->rm_line.reserve((size_t)reads * 4));
         HIP_TRY(c, hipMemsetAsync(c->rm_line.p, 0xFF, (size_t)reads * 4, c->stream));
@@ -5479,6 +5504,7 @@ static int stage_reads_chunk(wk_ctx* c, StageReads how, int64_t* n_reads, int64_
     c->chunk_valid = true;
     c->dx_chunk = !plain;
     c->rr_chunk = plain;
+    c->rd_chunk = keep;
     *n_reads = reads;
     *n_records = records;
     *status = 0;
@@ -5527,6 +5553,7 @@ int wk_dtok_stage_hits_demux(wk_ctx* c, const int32_t* genome_of_subject, int32_
     c->chunk_valid = false;
     c->dx_chunk = false;
     c->rr_chunk = false;
+    c->rd_chunk = false;
     c->dx_hits = false;
     c->ord_valid = false;
     const uint32_t lines = c->dt_lines;
@@ -5830,6 +5857,263 @@ int wk_dtok_readmap_lists(wk_ctx* c, int32_t job, int64_t* n_bytes) {
     return WK_OK;
 }
 
+// ---- read maps under demultiplexing on the device (wk_readmap_demux.hpp) -----------------------------------------
+
+static int64_t part_cap(const wk_ctx* c) { return c->pd_cap_opt ? c->pd_cap_opt : kPartCapDefault; }
+
+static PartArgs part_args(wk_ctx* c, const int32_t* samp, uint32_t n) {
+    PartArgs p{};
+    p.samp = samp;
+    p.n = n;
+    p.n_tiles = (n + kPartTile - 1) / kPartTile;
+    p.present = c->pd_present.as<uint32_t>();
+    p.n_cols = c->pd_state.as<uint32_t>();
+    p.flags = c->pd_state.as<uint32_t>() + 1;
+    p.total = c->pd_state.as<unsigned long long>() + 1;
+    p.mat = c->pd_mat.as<unsigned long long>();
+    p.col = c->pd_col.as<unsigned long long>();
+    p.seg = c->pd_seg.as<unsigned long long>();
+    p.off = c->pd_off.as<unsigned long long>();
+    return p;
+}
+
+// The columns of the samples samp[0, n) (device) holds, the segment table's ids: *n_cols = D.  Waits for the stream.
+static int part_columns(wk_ctx* c, const int32_t* samp, uint32_t n, uint32_t* n_cols) {
+    *n_cols = 0;
+    HIP_TRY(c, c->pd_present.reserve((size_t)kDemuxMaxSamples * 4));
+    HIP_TRY(c, c->pd_state.reserve(64));
+    HIP_TRY(c, c->pd_col.reserve((size_t)kDemuxMaxSamples * 8));
+    HIP_TRY(c, c->pd_seg.reserve((size_t)kDemuxMaxSamples * 3 * 8));
+    HIP_TRY(c, hipMemsetAsync(c->pd_present.p, 0, (size_t)kDemuxMaxSamples * 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->pd_state.p, 0, 16, c->stream));
+    const PartArgs p = part_args(c, samp, n);
+    if (n > 0) hipLaunchKernelGGL(readmap_demux_mark_kernel, dim3((n + kDtokThreads - 1) / kDtokThreads), dim3(kDtokThreads), 0, c->stream, p);
+    hipLaunchKernelGGL(readmap_demux_rank_kernel, dim3(1), dim3(kPartScanThreads), 0, c->stream, p);
+    HIP_TRY(c, hipGetLastError());
+    uint32_t st[2] = {0, 0};
+    HIP_TRY(c, hipMemcpyAsync(st, c->pd_state.p, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (st[1]) return fail(c, WK_E_RANGE, "a sample id beyond %u", kDemuxMaxSamples);
+    if (st[0] > kDemuxMaxSamples) return fail(c, WK_E_STATE, "the samples' columns do not add up");
+    *n_cols = st[0];
+    return WK_OK;
+}
+
+// Behind part_columns: the places off[r] of len[0, n) (device) in pd_off, the segment table, *total.  The caller has
+// checked tiles x n_cols against the capacity.  Waits for the stream.
+static int part_places(wk_ctx* c, const int32_t* samp, const unsigned long long* len, uint32_t n, uint32_t n_cols, unsigned long long* total) {
+    *total = 0;
+    if (n == 0 || n_cols == 0) return WK_OK;
+    const uint32_t tiles = (n + kPartTile - 1) / kPartTile;
+    if ((int64_t)tiles * n_cols > part_cap(c)) return fail(c, WK_E_CAPACITY, "%u tiles x %u samples beyond the partition's matrix", tiles, n_cols);
+    HIP_TRY(c, c->pd_mat.reserve((size_t)tiles * n_cols * 8));
+    HIP_TRY(c, c->pd_off.reserve((size_t)n * 8));
+    HIP_TRY(c, hipMemsetAsync(c->pd_mat.p, 0, (size_t)tiles * n_cols * 8, c->stream));
+    PartArgs p = part_args(c, samp, n);
+    p.len = len;
+    hipLaunchKernelGGL(readmap_demux_tile_kernel, dim3(tiles), dim3(kPartTile), 0, c->stream, p, n_cols);
+    hipLaunchKernelGGL(readmap_demux_columns_kernel, dim3((n_cols + kWave - 1) / kWave), dim3(kWave * kPartStrips), 0, c->stream, p, n_cols);
+    hipLaunchKernelGGL(readmap_demux_across_kernel, dim3(1), dim3(kPartScanThreads), 0, c->stream, p, n_cols);
+    hipLaunchKernelGGL(readmap_demux_add_kernel, dim3((n + kDtokThreads - 1) / kDtokThreads), dim3(kDtokThreads), 0, c->stream, p, n_cols);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(total, p.total, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return WK_OK;
+}
+
+// wk_dtok_stage_reads with the sample id of every read and the reads' leader lines kept, and the samples of the block
+// given their columns.  *status = 4: more tiles x samples than the partition's matrix holds -- no chunk is left staged and
+// nothing has been counted, the host tokenizer takes the block.  (The placement has run by then: the "met" bytes of the
+// block's samples are set on the device.  Nobody fetches them for a refused block -- wk_demux_fetch wants a staged chunk --
+// and the next staging clears them; the host route gives the same samples their columns.)
+int wk_dtok_stage_reads_samples(wk_ctx* c, int64_t* n_reads, int64_t* n_records, int* status) {
+    const int rc = stage_reads_demux(c, kStageDemuxKeep, n_reads, n_records, status);
+    if (rc || *status) return rc;
+    DeviceGuard guard(c->device);
+    c->rd_cols = 0;
+    uint32_t cols = 0;
+    int rc2 = WK_OK;
+    if (*n_reads > 0) rc2 = part_columns(c, c->rd_samp.as<int32_t>(), (uint32_t)*n_reads, &cols);
+    const int64_t tiles = (*n_reads + kPartTile - 1) / kPartTile;
+    if (rc2 || tiles * (int64_t)cols > part_cap(c)) {
+        c->chunk_valid = false;
+        c->dx_chunk = false;
+        c->rd_chunk = false;
+        *n_reads = *n_records = 0;
+        *status = 4;
+        return rc2;
+    }
+    c->rd_cols = cols;
+    return WK_OK;
+}
+
+// wk_dtok_readmap_reads / wk_dtok_readmap_lists under demultiplexing: the text of job `job` over the chunk of
+// wk_dtok_stage_reads_samples, one run per sample (*n_segments of them: wk_dtok_readmap_segments).
+static int readmap_demux_impl(wk_ctx* c, int32_t job, int64_t* n_bytes, int32_t* n_segments, bool lists) {
+    if (!c || !n_bytes || !n_segments) return WK_E_ARG;
+    *n_bytes = 0;
+    *n_segments = 0;
+    c->rm_bytes = 0;
+    c->rd_segs = 0;
+    if (!c->rd_chunk || !c->chunk_valid) return fail(c, WK_E_STATE, "no chunk staged by wk_dtok_stage_reads_samples");
+    if (c->rr_serial != c->stage_serial) return fail(c, WK_E_STATE, "the staged chunk's codes are not on the device (wk_classify_staged_keep)");
+    if (job < 0 || job >= c->rr_jobs) return fail(c, WK_E_ARG, "job must be in [0, %d)", c->rr_jobs);
+    if (c->n_reads >= (1ll << 32) - 1 || c->n_records >= (1ll << 31)) return fail(c, WK_E_RANGE, "more than 2^31 records in one block");
+    if (lists && c->rl_n != 0 && c->rl_n != c->rr_n)
+        return fail(c, WK_E_STATE, "the id table holds %d features, the shown-text table %d (wk_readmap_lists_ids)", c->rl_n, c->rr_n);
+    const uint32_t n_reads = (uint32_t)c->n_reads;
+    if (n_reads == 0 || c->dt_lines == 0 || c->rd_cols == 0) return WK_OK;
+    const int32_t* anc = nullptr;
+    if (lists && c->rl_mode[job] == WK_MODE_RANK) {
+        const int slot = c->rl_slot[job];
+        if (slot < 0 || slot >= (int)(sizeof c->rank_tab / sizeof c->rank_tab[0]) || !c->rank_tab_valid[slot])
+            return fail(c, WK_E_STATE, "job %d: rank slot %d has not been built", job, slot);
+        anc = c->rank_tab[slot].as<int32_t>();
+    }
+    DeviceGuard guard(c->device);
+    KtScope kt_scope(c);
+    HIP_TRY(c, c->rm_len.reserve((size_t)n_reads * 8));
+    HIP_TRY(c, c->rr_flags.reserve(16));
+    HIP_TRY(c, c->rr_off.reserve(4));  // (an empty table still has its first offset's place)
+    if (lists) {
+        HIP_TRY(c, c->rl_pairs.reserve((size_t)std::max<int64_t>(c->n_records, 1) * sizeof(uint2)));
+        HIP_TRY(c, c->rl_npairs.reserve((size_t)n_reads * 4));
+    }
+    DtokArgs a = dtok_args(c);
+    ReadmapListsArgs L{};
+    ReadmapReadsArgs& m = L.m;
+    m.assign = c->assign_out.as<int32_t>() + (size_t)job * n_reads;
+    m.read_line = c->rm_line.as<uint32_t>();
+    m.shown_off = c->rr_off.as<uint32_t>();
+    m.shown = c->rr_text.as<unsigned char>();
+    m.n_shown = (uint32_t)c->rr_n;
+    m.read_len = c->rm_len.as<unsigned long long>();
+    m.flags = c->rr_flags.as<uint32_t>();
+    m.n_reads = n_reads;
+    m.unassigned = c->rr_unassigned;
+    if (lists) {
+        L.subj = c->cur_subj;
+        L.qoff = c->cur_qoff;
+        L.subj_feat = c->subj_feat.as<int32_t>();
+        L.n_subjects = (uint32_t)std::max(c->n_subjects, 0);
+        L.anc = anc;
+        L.n_nodes = (uint32_t)std::max(c->n_nodes, 0);
+        L.key_off = c->rl_n ? c->rl_off.as<uint32_t>() : m.shown_off;
+        L.key = c->rl_n ? c->rl_text.as<unsigned char>() : m.shown;
+        L.pairs = c->rl_pairs.as<uint2>();
+        L.n_pairs = c->rl_npairs.as<uint32_t>();
+    }
+    const int32_t* samp = c->rd_samp.as<int32_t>();
+    const dim3 rgrid((n_reads + kDtokThreads - 1) / kDtokThreads);
+    HIP_TRY(c, hipMemsetAsync(c->rr_flags.p, 0, 16, c->stream));
+    // (the family's bracket is closed on every way out)
+    struct KtClose {
+        wk_ctx* c;
+        KernelTimer* t;
+        void close() {
+            if (t) ktimer_end(c, t);
+            t = nullptr;
+        }
+        ~KtClose() { close(); }
+    } kt{c, ktimer_begin(c, lists ? "readmap_lists_demux" : "readmap_reads_demux")};
+    if (lists)
+        hipLaunchKernelGGL(readmap_lists_build_demux_kernel, rgrid, dim3(kDtokThreads), 0, c->stream, a, L, samp);
+    else
+        hipLaunchKernelGGL(readmap_reads_len_demux_kernel, rgrid, dim3(kDtokThreads), 0, c->stream, a, m, samp);
+    HIP_TRY(c, hipGetLastError());
+    uint32_t flags = 0;
+    HIP_TRY(c, hipMemcpyAsync(&flags, c->rr_flags.p, 4, hipMemcpyDeviceToHost, c->stream));
+    unsigned long long total = 0;
+    const int rc = part_places(c, samp, m.read_len, n_reads, c->rd_cols, &total);
+    if (rc) return rc;
+    if (flags) {
+        return fail(c, WK_E_STATE, "job %d left a code or a list that the tables cannot print (%d features shown, %d subjects)", job, c->rr_n,
+                    c->n_subjects);
+    }
+    if (total >= (1ull << 40)) return fail(c, WK_E_RANGE, "read-map text of one block beyond 2^40 bytes");
+    if (total > 0) {
+        HIP_TRY(c, c->rm_text.reserve((size_t)total + 64));
+        m.out = c->rm_text.as<unsigned char>();
+        m.out_cap = total;
+        m.read_len = c->pd_off.as<unsigned long long>();  // (the places the partition gave the lines)
+        if (lists)
+            hipLaunchKernelGGL(readmap_lists_write_demux_kernel, rgrid, dim3(kDtokThreads), 0, c->stream, a, L, samp);
+        else
+            hipLaunchKernelGGL(readmap_reads_write_demux_kernel, rgrid, dim3(kDtokThreads), 0, c->stream, a, m, samp);
+        HIP_TRY(c, hipGetLastError());
+    }
+    kt.close();
+    c->rm_bytes = (int64_t)total;
+    c->rd_segs = (int32_t)c->rd_cols;
+    *n_bytes = (int64_t)total;
+    *n_segments = c->rd_segs;
+    return WK_OK;
+}
+
+int wk_dtok_readmap_reads_demux(wk_ctx* c, int32_t job, int64_t* n_bytes, int32_t* n_segments) {
+    return readmap_demux_impl(c, job, n_bytes, n_segments, false);
+}
+
+int wk_dtok_readmap_lists_demux(wk_ctx* c, int32_t job, int64_t* n_bytes, int32_t* n_segments) {
+    return readmap_demux_impl(c, job, n_bytes, n_segments, true);
+}
+
+int wk_dtok_readmap_segments(wk_ctx* c, uint64_t* seg, int32_t cap) {
+    if (!c || cap < 0 || (cap > 0 && !seg)) return WK_E_ARG;
+    if (cap < c->rd_segs) return fail(c, WK_E_CAPACITY, "need room for %d segments", c->rd_segs);
+    if (c->rd_segs == 0) return WK_OK;
+    DeviceGuard guard(c->device);
+    HIP_TRY(c, hipMemcpyAsync(seg, c->pd_seg.p, (size_t)c->rd_segs * 3 * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return WK_OK;
+}
+
+// (tests) the partition alone on arrays of the caller's.  *status = 1: tiles x samples beyond the capacity -- nothing
+// is written.
+int wk_readmap_demux_partition(wk_ctx* c, const int32_t* samp, const uint64_t* len, int64_t n, uint64_t* off, uint64_t* seg, int32_t seg_cap,
+                               int32_t* n_seg, uint64_t* total, int* status) {
+    if (!c || n < 0 || n >= (1ll << 32) - 1 || (n > 0 && (!samp || !len || !off)) || seg_cap < 0 || (seg_cap > 0 && !seg) || !n_seg || !total || !status)
+        return WK_E_ARG;
+    *status = 1;
+    DeviceGuard guard(c->device);
+    // (the staged chunk's columns and places are overwritten)
+    c->rd_chunk = false;
+    c->rd_segs = 0;
+    DevBuf d_samp, d_len;
+    struct Free {
+        DevBuf &a, &b;
+        ~Free() {
+            a.release();
+            b.release();
+        }
+    } free_bufs{d_samp, d_len};
+    HIP_TRY(c, d_samp.reserve((size_t)std::max<int64_t>(n, 1) * 4));
+    HIP_TRY(c, d_len.reserve((size_t)std::max<int64_t>(n, 1) * 8));
+    if (n > 0) {
+        HIP_TRY(c, hipMemcpyAsync(d_samp.p, samp, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d_len.p, len, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    uint32_t cols = 0;
+    int rc = part_columns(c, d_samp.as<int32_t>(), (uint32_t)n, &cols);
+    if (rc) return rc;
+    const int64_t tiles = (n + kPartTile - 1) / kPartTile;
+    if (tiles * (int64_t)cols > part_cap(c)) return WK_OK;
+    if ((int64_t)cols > seg_cap) return fail(c, WK_E_CAPACITY, "need room for %u segments", cols);
+    unsigned long long all = 0;
+    if ((rc = part_places(c, d_samp.as<int32_t>(), d_len.as<unsigned long long>(), (uint32_t)n, cols, &all))) return rc;
+    if (n > 0 && cols > 0) {
+        HIP_TRY(c, hipMemcpyAsync(off, c->pd_off.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(seg, c->pd_seg.p, (size_t)cols * 3 * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    } else {
+        for (int64_t r = 0; r < n; ++r) off[r] = 0;
+    }
+    *n_seg = (int32_t)cols;
+    *total = all;
+    *status = 0;
+    return WK_OK;
+}
+
 static bool ordinal_tally_jobs(const wk_ctx* c, const wk_job* jobs, int32_t n_jobs) {
     bool tally = c->use_tally && !c->genes_by_index && c->slots > 0;
     for (int j = 0; j < n_jobs && tally; ++j)
@@ -6005,6 +6289,7 @@ static int materialise_gene_lists(wk_ctx* c) {
     c->chunk_valid = true;
     c->dx_chunk = false;
     c->rr_chunk = false;
+    c->rd_chunk = false;
     return WK_OK;
 }
 

@@ -8,7 +8,9 @@ maps formatted there (csrc/wk_readmap.hpp) and the strata map joined there
 plain classification (csrc/wk_strata_reads.hpp, `_run_dstrata_reads`); read
 maps of whole-read assignments formatted there from the assignment codes
 (csrc/wk_readmap_reads.hpp, `_run_dreads_maps`), and those with taxon lists
-(csrc/wk_readmap_lists.hpp, `_run_dreads_lists`).
+(csrc/wk_readmap_lists.hpp, `_run_dreads_lists`), and either of a file that
+is demultiplexed, cut into one run per sample (csrc/wk_readmap_demux.hpp,
+`_run_dreads_demux`).
 Blocks the kernels leave alone go through the host tokenizer (`_host_block`)."""
 import os
 import time
@@ -20,6 +22,7 @@ import numpy as np
 from .. import _native as nat
 from ..hostio import (MAX_GROUPS, ROUTES, MapWriter, StageRing, peek_context,
                       tokenizer_threads)
+from .words import list_job
 
 
 _HOSTREG_SLOW = {}     # st_dev -> pinning that file system's pages in place is slower than reading them
@@ -1211,8 +1214,9 @@ class DeviceTextRoute:
                     self._tok_map_sent = self._tok_map.size
                 if status == 0:
                     if n_lines and self._ddemux is not None:
-                        yield None, ('ddemux', (text, fill, first, final,
-                                                hdr_in, hdr, n_lines)), \
+                        yield None, ('dreads_demux' if self._ddemuxmaps
+                                     is not None else 'ddemux', (
+                            text, fill, first, final, hdr_in, hdr, n_lines)), \
                             None, None, None, None
                     elif n_lines and self._dreads:
                         yield None, ('dreads', (text, fill, first, final,
@@ -1228,6 +1232,12 @@ class DeviceTextRoute:
                             text, fill, first, final, hdr_in, hdr, done)), \
                             None, None, None, None
                     tok.set_header_state(hdr)
+                elif self._ddemuxmaps is not None:
+                    # (the scan left the block to the host tokenizer:
+                    # `_run_dreads_demux` hands it over, no lines given)
+                    yield None, ('dreads_demux', (
+                        text, fill, first, final, hdr_in, hdr, None)), \
+                        None, None, None, None
                 else:
                     self._spec = False
                     yield from self._host_block(text, fill, first, final,
@@ -1944,6 +1954,135 @@ class DeviceTextRoute:
                                 packed_is_set=not self._dtrimsub)
         self.tok.set_header_state(hdr)
         return n
+
+    def _run_dreads_demux(self, data, packed, sample):
+        """A block the device has scanned for plain classification with read
+        maps of a file that is demultiplexed (`demux_read_maps_on_device`):
+        the samples its reads bring are registered as in `_run_ddemux`, the
+        block is staged as a CSR chunk with a group and a sample id per read
+        (`wk_dtok_stage_reads_samples`) and counted with the assignment codes
+        left on the device (`wk_classify_staged_keep`); per rank the map text
+        is formatted there as one run per sample
+        (`wk_dtok_readmap_lists_demux` if the set holds a job able to return
+        a list, else `wk_dtok_readmap_reads_demux`), and every run is appended
+        to its sample's file through the sequencing thread.  A block the
+        kernels refuse -- more samples than the table holds, a read of more
+        subjects than a count key can say, more tiles x samples than the
+        partition takes -- goes through the host tokenizer, the host's
+        demultiplexing and the host formatter, and lands in the same files in
+        order."""
+        buf, fill, first, final, hdr_in, hdr, n_lines = packed[1]
+        allow, rank2dir, outzip, namedic = self._ddemuxmaps
+        lists = any(map(list_job, self.jobs))
+        self._sync_subjects(data)
+        status, fresh = (1, []) if self._dx_full or n_lines is None \
+            else self.ctx.demux_pending()
+        if status == 0:
+            names = self._dx_names
+            if fresh:
+                names.extend(x.decode() for x in fresh)
+            # room for the groups and the count keys the block can add (before
+            # its groups are taken: a fold numbers them anew)
+            if len(self.groups) + len(names) + 1 >= MAX_GROUPS // 2:
+                self.collect(data)
+            self._ensure_table(data, n_lines, min(n_lines, len(names) + 1))
+            key = (self._epoch, len(names))
+            if fresh or self._dx_key != key:
+                self.ctx.demux_register(fresh,
+                                        self._device_sample_groups(allow))
+                self._dx_key = key
+            status, n_reads, _ = self.ctx.dtok_stage_reads_samples()
+        elif status & 1 and n_lines is not None:
+            self._dx_full = True    # (the rest of the file: the host's)
+        if status == 0:
+            ROUTES['dreads_demux'] += 1
+            if n_reads:
+                self._sync_shown(namedic, ids=lists)
+                self.ctx.classify_staged_keep(self.jobs)
+                met, _ = self.ctx.demux_fetch(len(self._dx_names))
+                for i in np.flatnonzero(met).tolist():
+                    s = self._dx_names[i]
+                    for rank in self.ranks:
+                        data[rank].setdefault(s, {})
+                self._device_maps_demux(rank2dir, outzip, lists)
+            self._n_reads += n_reads
+            return n_reads
+        from ..workflow import demux_labels
+        n = 0
+        for _, (subj, qoff), _, names, *_ in self._host_block(
+                buf, fill, first, final, hdr_in, names=True):
+            reads = nat.Tokenizer.query_names(*names)
+            sample_of, reads = demux_labels(reads, allow)
+            # (the Python writer opens the files itself: what the sequencing
+            # thread still holds goes in front)
+            self._maps_done()
+            if self._writer is not None:
+                self._writer.flush()
+            n += self._run_general(
+                data, reads, None, sample_of, None, None, rank2dir, outzip,
+                namedic, False, (subj, qoff), None, None, None, None, allow,
+                not self._dtrimsub)
+        self.tok.set_header_state(hdr)
+        return n
+
+    def _device_maps_demux(self, rank2dir, outzip, lists):
+        """The read maps of the chunk `wk_dtok_stage_reads_samples` staged
+        last: per rank the text from the device, cut into one run per sample
+        (`wk_dtok_readmap_*_demux`, the segment table next to it), every run
+        appended to its sample's file behind this thread's back -- a sample
+        all of whose reads leave no line still gets its file, as
+        `file.write_readmap` opens it."""
+        if self._mring is None:
+            self._mring = StageRing(self.ctx, 6, {
+                'text': (np.uint8, self.MAP_TEXT_SLOT)})
+        if self._map_pool is None:
+            from concurrent.futures import ThreadPoolExecutor
+            self._map_pool = ThreadPoolExecutor(max_workers=self.MAP_THREADS)
+            self._map_seq = ThreadPoolExecutor(max_workers=1)
+        if self._writer is None:
+            self._writer = MapWriter()
+        ring = self._mring
+        names = self._dx_names
+        for j, rank in enumerate(self.ranks):
+            if rank not in rank2dir:
+                continue
+            bufs = ring.try_current()
+            while bufs is None:     # every buffer waits for its text to be written
+                self._maps_done()
+                self._writer._drain(True, one=True)
+                bufs = ring.try_current()
+            text, inside, seg = self.ctx.dtok_readmap_demux(
+                j, lists=lists, out=bufs['text'])
+            if not seg.shape[0]:
+                continue
+            slot = ring.take() if inside and text.size else None
+            runs = []
+            for sid, lo, nb in seg.tolist():
+                outfp = join(rank2dir[rank], f'{names[sid]}.txt')
+                runs.append((f'{outfp}.{outzip}' if outzip else outfp,
+                             text[lo:lo + nb]))
+            # (through the sequencing thread: blocks the host formatted are
+            # appended from there too, in order)
+            self._maps_done(keep=4 * self.MAP_THREADS)
+            self._map_jobs.append(self._map_seq.submit(
+                self._append_runs, runs, outzip,
+                None if slot is None else partial(ring.release, slot)))
+
+    def _append_runs(self, runs, outzip, done):
+        """(on the sequencing thread) the runs of one block's text to their
+        samples' files; ``done()`` once the last of them has been written."""
+        # (a run that is compressed is read from the ring's buffer until it
+        # has been written; the others are copied here)
+        held = [k for k, (_, text) in enumerate(runs) if outzip and len(text)]
+        last = held[-1] if held else None
+        for k, (path, text) in enumerate(runs):
+            if outzip and len(text):
+                self._writer.append(path, text, outzip,
+                                    done if k == last else None)
+            else:
+                self._writer.append(path, bytes(text), outzip)
+        if last is None and done is not None:
+            done()
 
     def _sync_map_tables(self, namedic):
         """The device's read-map tables (wk_readmap_tables) over the subject

@@ -188,6 +188,34 @@ class WordsRoute:
             return False
         return any(map(list_job, self.jobs))
 
+    def demux_read_maps_on_device(self, fmt, demux=True, strata=False,
+                                  coords=False, outcov=False, part=None,
+                                  own_text=True):
+        """Can the read maps of this file be formatted on the device although
+        the file is demultiplexed (csrc/wk_readmap_demux.hpp,
+        `_run_dreads_demux`)?  Plain classification with `--outmap` of a file
+        that is demultiplexed (``demux``: `--demux`, or a single-file input):
+        the whole file (``part``) of SAM, BLAST tabular, PAF or simple-map
+        text that can be read block by block (``own_text``: a plain file or a
+        gzip file this package inflates itself), with or without `--trim-sub`
+        / `--exclude`, `--samples`, `--unassigned`, `--name-as-id`; 1 to
+        `MAX_JOBS` jobs of any kind, none size-normalised (a set with a job
+        able to return a list is formatted by the list formatter, every other
+        set by the formatter of whole-read assignments).  Not under
+        ``strata``, ``coords``, ``outcov`` or `--sizes`, not during the replay
+        pass.  ``WOLTKA_NO_DDEMUXMAPS=1`` (like ``WOLTKA_NO_DDEMUX=1`` and
+        ``WOLTKA_NO_DTOK=1``) keeps the host route."""
+        if os.environ.get('WOLTKA_NO_DDEMUXMAPS') or \
+                os.environ.get('WOLTKA_NO_DDEMUX') or \
+                os.environ.get('WOLTKA_NO_DTOK'):
+            return False
+        if not demux or strata or coords or outcov or self.sizes or \
+                self._replay is not None or part is not None or \
+                not own_text or fmt not in ('sam', 'b6o', 'paf', 'map') or \
+                not 1 <= len(self.jobs) <= nat.MAX_JOBS:
+            return False
+        return not any(job.flags & nat.F_SIZED for job in self.jobs)
+
     def _run_words(self, data, packed, sample):
         """One chunk of packed records (``('words', array, n_reads, slot)``
         from `native_chunks`): appended to the sample's records on the device,

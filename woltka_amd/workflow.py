@@ -559,6 +559,24 @@ def classify(
                                         isinstance(stream, GunzipStream))):
                                 dlistmaps = (rank2dir, outzip, namedic)
                                 dmaps = None
+                        # ... and of a file that is demultiplexed: any job
+                        # set, the text cut into one run per sample on the
+                        # device (csrc/wk_readmap_demux.hpp)
+                        ddemuxmaps = None
+                        if rank2dir is not None and demux:
+                            from .file import ZIP_BY_EXT, GunzipStream
+                            from os.path import splitext
+                            if engine.demux_read_maps_on_device(
+                                    fmt_, demux=True,
+                                    strata=bool(stratmap),
+                                    coords=bool(ordinal),
+                                    outcov=cover is not None, part=part,
+                                    own_text=path != '-' and (
+                                        ZIP_BY_EXT.get(splitext(path)[1])
+                                        is None or
+                                        isinstance(stream, GunzipStream))):
+                                ddemuxmaps = (allow, rank2dir, outzip,
+                                              namedic)
                         chunks = engine.native_chunks(
                             stream, head, exclude, NATIVE_BLOCK, ordinal,
                             want_names, trimsub, want_groups=native_strata,
@@ -581,7 +599,7 @@ def classify(
                                 n_jobs=len(engine.jobs),
                                 replay=engine._replay is not None) else None,
                             dreads=dreads, dreadmaps=dreadmaps,
-                            dlistmaps=dlistmaps)
+                            dlistmaps=dlistmaps, ddemuxmaps=ddemuxmaps)
                         if ordinal and rank2dir is not None:
                             chunks = engine.regroup_hits(chunks, n)
                     else:
